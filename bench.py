@@ -7,8 +7,15 @@ SD_SHARD_MODE=range for contiguous basis-index ranges).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-A step = one pass of the hot path: out <- H psi on a random normalised psi resident in HBM (ping-pong
-between two buffers; for N > 1 each step includes the RCCL halo exchange).  Rank 0 prints ONE JSON line.
+A step = one pass of the hot path: out <- H psi on a random normalised psi resident in HBM (every step reads the same
+psi and writes the same out, so the last step's output is H psi for any K; for N > 1 each step includes the RCCL halo
+exchange).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the benchmark
+measures or checks: the exactness self-checks before timing, the CPU baseline (unless --no-cpu) and, for N > 1, the
+kernel-only timing behind `roofline` and the per-rank breakdown `per_rank_ms`.  --dump-outputs DIR writes a fixed, seeded
+sample of the last step's output: DIR/Hpsi.npy (float64; [re, im] columns for c128) and DIR/rows.npy (their global basis
+indices, as float64).
 """
 import argparse
 import json
@@ -22,6 +29,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0      # MI355X spec HBM3E peak (MI355X_MICROARCH.md)
 HBM_COPY_GBS = 6290.0      # the guide's measured float4-copy ceiling: quoted beside the spec fraction
 SEED = 20260821
+DUMP_ROWS = 1 << 20        # --dump-outputs: sampled rows of a larger output (c128: 16 MB of values + 8 MB of indices)
 # sources whose change invalidates a committed PMC traffic figure (profiles/collect_traffic.py stamps their hash)
 TRAFFIC_SOURCES = ["spindynamics.jl_amd/csrc/kernels_apply.hip", "spindynamics.jl_amd/csrc/device_common.hpp",
                    "spindynamics.jl_amd/csrc/basis.cpp", "spindynamics.jl_amd/csrc/sd_internal.hpp"]
@@ -183,6 +191,8 @@ def main():
     ap.add_argument("--L", type=int, default=int(os.environ.get("SD_BENCH_L", "32")))
     ap.add_argument("--dtype", default="c128", choices=["c128", "f64"])
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the self-checks, the CPU baseline and the N > 1 breakdowns")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a seeded sample of the last step's output as .npy files")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -303,6 +313,8 @@ def main():
     check = "uniform state exact eigenvector on all ranks"
     if os.environ.get("SD_DEBUG_SKIP", "0") not in ("", "0"):
         check = "SKIPPED: SD_DEBUG_SKIP timing ablation (results are wrong by construction)"
+    elif not args.full:
+        check = "not run (plain run; --full runs the self-checks)"
     else:
         good = selfcheck()
         if good and world > 1:
@@ -328,6 +340,41 @@ def main():
     a /= nrm
     b.zero_()
 
+    def dump_outputs(out, path):
+        """The last step's output at DUMP_ROWS global basis indices drawn with SEED (all rows when N is smaller), gathered
+        on rank 0 from the ranks that own them and written as float64: Hpsi.npy ([re, im] columns for c128), rows.npy."""
+        import numpy as np
+        rows = np.arange(model.N, dtype=np.int64)
+        if model.N > DUMP_ROWS:
+            rows = np.unique(np.random.default_rng(SEED).integers(0, model.N, DUMP_ROWS))
+        lb, gb, ln = model.local_tiles()            # local row lb+i <-> global row gb+i
+        order = np.argsort(gb)
+        lb, gb, ln = lb[order], gb[order], ln[order].astype(np.int64)
+        t = np.searchsorted(gb, rows, side="right") - 1
+        own = t >= 0
+        own[own] = rows[own] < gb[t[own]] + ln[t[own]]
+        local = lb[t[own]] + rows[own] - gb[t[own]]
+        if len(local) and not (local.min() >= 0 and local.max() < out.numel()):
+            raise SystemExit("bench.py: --dump-outputs: a local row outside this rank's vector")
+        vals = out[torch.from_numpy(local).to(out.device)]
+        vals = torch.view_as_real(vals) if vals.is_complex() else vals
+        parts = [(np.flatnonzero(own), vals.cpu().numpy())]
+        if dist is not None:
+            mine, parts = parts[0], [None] * world
+            dist.all_gather_object(parts, mine)
+        if rank != 0:
+            return
+        got = np.full((len(rows),) + parts[0][1].shape[1:], np.nan)
+        seen = np.zeros(len(rows), bool)
+        for pos, v in parts:
+            got[pos] = v
+            seen[pos] = True
+        if not seen.all():
+            raise SystemExit("bench.py: --dump-outputs: %d sampled rows are owned by no rank" % (~seen).sum())
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "Hpsi.npy"), got)
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+
     def sync():
         if dist is not None:
             dist.barrier()
@@ -335,10 +382,10 @@ def main():
 
     def timed(apply_fn, src, dst):
         """W untimed + K timed steps of apply_fn(dst, src) bracketed by barrier + synchronize; the MAX over the ranks of the
-        wall time, the device time per step on the launch stream, the sorted per-step device times, and where src / dst ended."""
+        wall time, the device time per step on the launch stream, the sorted per-step device times, and src / dst.  Every
+        step reads the same src: a chain of applies would grow like |E0|^steps and overflow float64 after a few hundred."""
         for _ in range(args.warmup):
             apply_fn(dst, src)
-            src, dst = dst, src
         sync()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # per-step device times (median / min)
@@ -347,7 +394,6 @@ def main():
         marks[0].record()
         for k in range(args.steps):
             apply_fn(dst, src)
-            src, dst = dst, src
             marks[k + 1].record()
         ev1.record()
         sync()
@@ -364,21 +410,20 @@ def main():
     elapsed, ev_ms, step_ms, src, dst = timed(lambda d, s_: op.apply(d, s_), a, b)
     path_used = "python: torch.distributed point-to-point issued per step" if world > 1 else "single rank"
 
-    # kernel-only timing (no exchange) for the roofline of the dominant kernel: HIP events around K launches
-    kern_ms = ev_ms
-    if world > 1:
+    # kernel-only timing (no exchange) for the roofline of the dominant kernel: HIP events around K launches (N > 1: --full)
+    kern_ms = ev_ms if world == 1 else None
+    if world > 1 and args.full:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(args.steps):
             op.apply(dst, src, exchange=False)
-            src, dst = dst, src
         e1.record()
         torch.cuda.synchronize()
         kern_ms = e0.elapsed_time(e1) / args.steps
 
-    # ---- N > 1: where a step's time goes on every rank ----
+    # ---- N > 1: where a step's time goes on every rank (--full) ----
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         prof = [op.apply_profiled(dst, src) for _ in range(3)][-1]
         prof["rank"] = rank
         prof["rows_owned"], prof["rows_imported"] = op.n_local, op.n_halo
@@ -392,7 +437,7 @@ def main():
         N = model.N
         ms_per_step = elapsed / args.steps * 1e3
         alg_bytes = op.n_local * 2 * esize               # read psi[idx] once + write out[idx] once
-        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9    # GB/s on this rank's GPU
+        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms is not None else None   # GB/s on this rank's GPU
         # HBM-side bytes per apply from the PMC counters (2*FETCH_SIZE + WRITE_SIZE, gfx950 correction): collected by
         # profiles/run_profile.sh in separate rocprofv3 passes and committed with the hash of the kernel sources it was
         # measured on.  A figure measured on other sources is not reported.
@@ -437,7 +482,7 @@ def main():
                        "path": path_used, "library_path": library_path},
             "selfcheck": check,
             "achieved_hbm_GBs_per_gpu": achieved,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "roofline": None if kern_ms is None else {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "frac_of_copy_ceiling": achieved / HBM_COPY_GBS,
                          "traffic": traffic, "traffic_source": traffic_source,
                          # the verdict on the 0.60 target in numbers: how many times the algorithmic bytes
@@ -528,7 +573,6 @@ def main():
                         tinfo["status"] = "no route brings the busiest link below 0.9 of the busiest direct message: direct exchange kept"
                         return tinfo, None
                     op._routes = False
-                    op.fill_randn(src, SEED)
                     h_direct = op.exchange(src).clone()
                     ref = torch.empty_like(dst)
                     apply_head(ref, src)
@@ -562,8 +606,10 @@ def main():
                 if tres is not None:
                     line = build_line(tres[0], tres[1], head_path + ", halo over pipelined two-hop relays", info)
                 line["config"]["relay_trial"] = tinfo
+    if args.dump_outputs:
+        dump_outputs(dst, args.dump_outputs)
     if rank == 0:
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             try:
                 line["cpu_baseline"] = cpu_baseline(L, nup)
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number

@@ -319,7 +319,7 @@ def test_bench_starts_its_own_ranks_two_processes_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["SD_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--L", "24", "--steps", "5",
-                        "--warmup", "1"], cwd=root, capture_output=True, text=True, timeout=600, env=env)
+                        "--warmup", "1", "--full"], cwd=root, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
