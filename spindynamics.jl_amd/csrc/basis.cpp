@@ -3,9 +3,7 @@
 // src/Basis.jl:37-53) from binomial coefficients only: no states[] array and
 // no hash map are ever built for the full dimension.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -142,18 +140,13 @@ static int count_nn_hops(const sd_model *m) {
 // DISJOINT flippable top bonds (the odd prefix bonds (1,2),(3,4),..: flipping one never changes another) form orbits
 // of 2^f tiles; the members of an orbit are queued back to back on ONE XCD, so that a member's partner reads for
 // those bonds -- the first far bonds it processes, right after its own rows were fetched by the partner -- hit
-// that XCD's L2 (or merge with the in-flight fetch) instead of going to the fabric again.  SD_XCD_ORBIT = max f
-// (0 disables, then SD_XCD_CHUNK consecutive tiles per XCD are used).  Speed only: a bijection of the tile list.
+// that XCD's L2 (or merge with the in-flight fetch) instead of going to the fabric again.  FO = max f; plans without
+// orbits (too few tiles, p < 3, no chain) deal runs of CH consecutive tiles to each XCD.  Speed only: a bijection of the tile list.
 static void xcd_order(const sd_model *m, int p, std::vector<uint32_t> &tp_io, std::vector<int64_t> &tb_io,
                       std::vector<int64_t> &first_seen) {
   {
-    int FO = 5;     // measured with 5 workgroups per CU in flight (profiles/ablation_r02.md §14): 5 beats 6 by 1 % at L=28..32
-    if (const char *e = getenv("SD_XCD_ORBIT")) FO = atoi(e);
-    if (FO > 8) FO = 8;
-    int CH = 32;
-    if (const char *e = getenv("SD_XCD_CHUNK")) CH = atoi(e);
-    int B0 = 1;     // first bond considered as an orbit generator (two-pass probe: the bonds below belong to the other pass)
-    if (const char *e = getenv("SD_XCD_ORBIT_FROM")) B0 = std::max(1, atoi(e));
+    const int FO = 5;     // measured with 5 workgroups per CU in flight (profiles/ablation_r02.md §14): 5 beats 6 by 1 % at L=28..32
+    const int CH = 32;
     const size_t nt = tp_io.size();
     // (Tried: the "transposed" order -- tiles sorted by (filling of the prefix, prefix as an integer: site 1 varies fastest), dealt to
     // the XCDs in runs of K.  The LRU model of profiles/l2_order_lab.py (pasc<K>) promises 25 % fewer read misses; the hardware
@@ -162,22 +155,19 @@ static void xcd_order(const sd_model *m, int p, std::vector<uint32_t> &tp_io, st
     // (Tried: with a wrap bond (1, j), j in the suffix -- the periodic chain's (L, 1) -- site 1 alone as an extra generator, so
     // that P and P ^ 1 are queued next to each other and the wrap bond's gather finds its partner tile in L2.  Periodic L=28 /
     // L=30: 0.775 / 3.127 ms with it, 0.770 / 3.117 without -- no gain, removed; profiles/ablation_r03.md section 5.)
-    const bool wrap = false;
-    const int Bp = wrap ? 2 : B0, FOp = wrap ? std::max(FO - 1, 0) : FO;
-    // canonical orbit representative: chosen pairs set to (up, down) (site 1 down with a wrap bond); member id = what is flipped
+    // canonical orbit representative: chosen pairs set to (up, down); member id = what is flipped
     auto canon = [&](uint32_t P, int *member_out) {
-      uint32_t C0 = P; int member = 0, ng = 0, sh = 0;
-      if (wrap) { member = (int)(P & 1u); C0 &= ~1u; sh = 1; }
-      for (int b = Bp; b + 1 <= p && ng < FOp; b += 2)
+      uint32_t C0 = P; int member = 0, ng = 0;
+      for (int b = 1; b + 1 <= p && ng < FO; b += 2)
         if (((P >> (b - 1)) ^ (P >> b)) & 1u) {
-          if (!((P >> (b - 1)) & 1u)) { C0 ^= 3u << (b - 1); member |= 1 << (ng + sh); }
+          if (!((P >> (b - 1)) & 1u)) { C0 ^= 3u << (b - 1); member |= 1 << ng; }
           ++ng;
         }
       if (member_out) *member_out = member;
       return C0;
     };
     auto first_seen_reset = [&](uint32_t P) { first_seen[canon(P, nullptr)] = -1; };
-    if (FO > 0 && nt >= 64 && p >= 3 && count_nn_hops(m) > 0) {
+    if (nt >= 64 && p >= 3 && count_nn_hops(m) > 0) {
       std::vector<uint64_t> key(nt);     // (first-seen rank of the orbit) << 8 | member id
       int64_t n_orb = 0;
       for (size_t k = 0; k < nt; ++k) {
@@ -192,12 +182,10 @@ static void xcd_order(const sd_model *m, int p, std::vector<uint32_t> &tp_io, st
       // deal whole orbits to the 8 XCD queues, then interleave the queues (position j of queue x -> block 8j + x)
       std::vector<std::vector<size_t>> q(8);
       size_t o = 0;
-      size_t OC = 1;   // consecutive orbits handed to the same XCD
-      if (const char *e = getenv("SD_XCD_ORBIT_RUN")) OC = (size_t)std::max(1, atoi(e));
       for (size_t k = 0; k < nt;) {
         size_t e = k;
         while (e < nt && (key[idx[e]] >> 8) == (key[idx[k]] >> 8)) ++e;
-        for (size_t t = k; t < e; ++t) q[(o / OC) % 8].push_back(idx[t]);
+        for (size_t t = k; t < e; ++t) q[o % 8].push_back(idx[t]);
         ++o; k = e;
       }
       std::vector<uint32_t> tp; std::vector<int64_t> tb;
@@ -209,7 +197,7 @@ static void xcd_order(const sd_model *m, int p, std::vector<uint32_t> &tp_io, st
           if (j < q[x].size()) { tp.push_back(tp_io[q[x][j]]); tb.push_back(tb_io[q[x][j]]); }
       for (size_t k = 0; k < nt; ++k) first_seen_reset(tp_io[k]);
       tp_io.swap(tp); tb_io.swap(tb);
-    } else if (CH > 0 && nt >= (size_t)16 * CH) {
+    } else if (nt >= (size_t)16 * CH) {
       std::vector<uint32_t> tp(nt);
       std::vector<int64_t> tb(nt);
       const size_t group = (size_t)8 * CH, full = nt / group * group;
@@ -338,8 +326,6 @@ static bool best_bisect_plan(const sd_model *m, int p, int nranks, BisectPlan &b
       for (int s3 = (d > 2 ? s2 + 2 : s2); s3 <= (d > 2 ? p - 1 : s2); ++s3) {
         bp.s[0] = 0; bp.s[1] = s1; bp.s[2] = s2; bp.s[3] = s3;
         if (!eval_bisect(m, bp)) continue;
-        if (getenv("SD_SHARD_DEBUG") && atoi(getenv("SD_SHARD_DEBUG")) > 1)
-          fprintf(stderr, "[sd shard]   s=(%d,%d,%d) import %.3f busiest %.3g\n", s1, s2, s3, bp.score, bp.busiest);
         // the worst rank's import first, then the busiest pair (xGMI is point to point)
         if (!found || bp.score < best.score * (1 - 1e-12) ||
             (bp.score <= best.score * (1 + 1e-12) && bp.busiest < best.busiest)) { best = bp; found = true; }
@@ -374,19 +360,16 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
       m->max_tile_len_all = std::max<int>(m->max_tile_len_all, (int)std::min<int64_t>(B(m, LS, t), 1 << 30));
   // (Prefix spaces beyond 2^26 -- dilute sectors of chains with L >= 39 at LS = 12 -- keep the per-row path: the plan's dense prefix
   // tables cost 13 B x 2^p on the host and its tile order visits all 2^p prefixes; measured with the cap at 28: L=40, nup=10 plans in
-  // 110 s for an apply of ~50 instead of 528 ms, profiles/ablation_r04.md section 11.  SD_PLAN_TIMING=1 prints where a plan's seconds go.)
+  // 110 s for an apply of ~50 instead of 528 ms, profiles/ablation_r04.md section 11.)
   // Small, very dilute sectors: with fewer than 32 rows per tile on average and fewer than 1.5 M rows in all the apply is a handful of
   // launches of mostly one-row workgroups, and the per-row path's single launch is as fast or faster (L=30, nup=6: 12.0 against 9.3 G
   // rows/s; L=32, nup=6: 13.4 against 13.2; larger dilute sectors go to the tiles, whose short ones have a kernel of their own:
   // L=36, nup=6: 17.1 against 14.2 -- profiles/ablation_r04.md section 11).  Unsharded plans only: a shard is a union of tiles.
-  // SD_FORCE_PER_ROW / SD_FORCE_TILED: A/B.
   bool short_tiles = false;
   if (m->nup >= 0 && p >= 0 && p <= SD_MAX_PREFIX_BITS && nranks == 1) {
     double nt = 0;
     for (int k = std::max(0, m->nup - LS); k <= std::min(p, m->nup); ++k) nt += (double)B(m, p, k);
     short_tiles = nt > 0 && (double)m->N / nt < 32.0 && p >= 1 && m->N < 1500000;
-    if (getenv("SD_FORCE_PER_ROW")) short_tiles = true;
-    if (getenv("SD_FORCE_TILED")) short_tiles = false;
   }
   if (m->nup < 0 || p > SD_MAX_PREFIX_BITS || short_tiles) {
     // generic (untiled) path: per-row rank/unrank on device
@@ -395,7 +378,7 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
     m->shard_mode = 0; m->n_interior = 0; m->fs_dbits = 0;
     m->pack_src.clear(); m->pack_dst.clear(); m->pack_len.clear(); m->n_send = 0;
     // full 2^L basis: idx = state, so 2^10 consecutive rows form a tile without any table (k_apply_fulltile)
-    m->full_ls = (m->nup < 0 && L >= 12 && L <= 40 && !getenv("SD_NO_FULLTILE")) ? 10 : 0;
+    m->full_ls = (m->nup < 0 && L >= 12 && L <= 40) ? 10 : 0;
     if (nranks == 1) return SD_OK;
     // Full basis over 2^d ranks (src/Hamiltonian.jl:223,255-257: idx = state): the rank is the top d index bits, i.e. the
     // configuration of sites L-d+1..L; a rank owns the contiguous rows [r N/P, (r+1) N/P).  Chain bonds below site L-d stay
@@ -484,15 +467,6 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
     }
   }
 
-  // SD_PLAN_TIMING=1: where the seconds of a plan go (stderr)
-  const bool timing = getenv("SD_PLAN_TIMING") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto tick = [&](const char *what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[sd plan] %-28s %.3f s\n", what, std::chrono::duration<double>(now - t_last).count());
-    t_last = now;
-  };
   // all feasible tiles in natural (row) order
   std::vector<TileRef> tiles;
   const uint32_t nP = 1u << p;
@@ -504,7 +478,6 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
   std::sort(tiles.begin(), tiles.end(), [](const TileRef &a, const TileRef &b) { return a.base < b.base; });
   const size_t T = tiles.size();
   if (T == 0) { err = "empty basis"; return SD_EINTERNAL; }
-  tick("tiles enumerated + sorted");
 
   // ---- ownership of every tile ----
   // mode 0 ("range"): contiguous, tile-aligned basis-index ranges (what BASELINE.json's north star names).
@@ -564,10 +537,7 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
       }
     // nested bisections (nranks = 2, 4, 8) when they import less than the run-of-cells cut
     BisectPlan bis;
-    const bool have_bis = !getenv("SD_SHARD_NO_BISECT") && best_bisect_plan(m, p, nranks, bis);
-    if (getenv("SD_SHARD_DEBUG"))
-      fprintf(stderr, "[sd shard] cells (m1=%d, m2=%d) worst import %.3f | bisections found=%d d=%d s=(%d,%d,%d) worst import %.3f busiest pair %.3g rows\n",
-              bm1, bm2, best, (int)have_bis, bis.d, bis.s[1], bis.s[2], bis.s[3], bis.score, bis.busiest);
+    const bool have_bis = best_bisect_plan(m, p, nranks, bis);
     if (have_bis && (bm1 < 0 || bis.score < best)) {
       for (size_t k = 0; k < T; ++k) {
         int cnt[3] = {0, 0, 0};
@@ -583,62 +553,56 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
       // weighted median.  The bonds inside those K sites now cross the cut too, but each with a fraction of the rows that sat at
       // the integer threshold: at L=32, 8 ranks the import is unchanged (333 M rows in all, busiest pair 17.8 M) and the ranks
       // own 71.2-77.4 M rows (K = 3).  Kept only if it does not cross more bonds (x 1.05) than the integer cut.
-      int K = 3;
-      if (const char *e = getenv("SD_SHARD_FINE")) K = std::max(0, std::min(6, atoi(e)));
-      if (K > 0) {
-        std::vector<int> fine(T, 0);
-        std::vector<int32_t> idx_of((size_t)nP, -1);
-        for (size_t k = 0; k < T; ++k) idx_of[tiles[k].P] = (int32_t)k;
-        for (int lev = 0; lev < bis.d; ++lev) {
-          const int sb = bis.s[bis.d - lev], kk = std::min(K, p - sb);
-          const uint32_t bmask = (1u << sb) - 1u;
-          auto zof = [&](uint32_t P) {
-            uint32_t z = (uint32_t)__builtin_popcount(P & bmask);
-            for (int j = 0; j < kk; ++j) z = 2 * z + ((P >> (sb + j)) & 1u);
-            return z;
-          };
-          const size_t nz = ((size_t)sb + 1) << kk;
-          std::vector<double> hist((size_t)(1 << lev) * nz, 0.0);
-          for (size_t k = 0; k < T; ++k) hist[(size_t)fine[k] * nz + zof(tiles[k].P)] += (double)tlen[k];
-          std::vector<uint32_t> thr((size_t)1 << lev, 0);
-          for (int pre = 0; pre < (1 << lev); ++pre) {
-            const double *h = hist.data() + (size_t)pre * nz;
-            double tot = 0; for (size_t z = 0; z < nz; ++z) tot += h[z];
-            double acc = 0, bestd = 1e300;
-            for (size_t z = 0; z + 1 < nz; ++z) {
-              acc += h[z];
-              const double dd = std::fabs(acc - tot / 2);
-              if (dd < bestd) { bestd = dd; thr[pre] = (uint32_t)z; }
-            }
-          }
-          for (size_t k = 0; k < T; ++k) fine[k] = 2 * fine[k] + (zof(tiles[k].P) > thr[fine[k]] ? 1 : 0);
-        }
-        // rows whose hop partner lives on another rank (partner tiles counted once per reading tile), largest rank
-        auto judge = [&](const std::vector<int> &own, double &crossing, double &largest) {
-          crossing = 0;
-          std::vector<double> size(nranks, 0.0);
-          for (size_t k = 0; k < T; ++k) {
-            const uint32_t P = tiles[k].P;
-            size[own[k]] += (double)tlen[k];
-            for (int b = 1; b <= p - 1; ++b)
-              if (((P >> (b - 1)) ^ (P >> b)) & 1u) {
-                const int32_t j = idx_of[P ^ (3u << (b - 1))];
-                if (j >= 0 && own[j] != own[k]) crossing += (double)tlen[j];
-              }
-          }
-          largest = 0;
-          bool empty = false;
-          for (double v : size) { largest = std::max(largest, v); if (v <= 0) empty = true; }
-          return !empty;
+      const int K = 3;
+      std::vector<int> fine(T, 0);
+      std::vector<int32_t> idx_of((size_t)nP, -1);
+      for (size_t k = 0; k < T; ++k) idx_of[tiles[k].P] = (int32_t)k;
+      for (int lev = 0; lev < bis.d; ++lev) {
+        const int sb = bis.s[bis.d - lev], kk = std::min(K, p - sb);
+        const uint32_t bmask = (1u << sb) - 1u;
+        auto zof = [&](uint32_t P) {
+          uint32_t z = (uint32_t)__builtin_popcount(P & bmask);
+          for (int j = 0; j < kk; ++j) z = 2 * z + ((P >> (sb + j)) & 1u);
+          return z;
         };
-        double c0 = 0, l0 = 0, c1 = 0, l1 = 0;
-        judge(owner, c0, l0);
-        const bool ok1 = judge(fine, c1, l1);
-        if (getenv("SD_SHARD_DEBUG"))
-          fprintf(stderr, "[sd shard] fine thresholds (K=%d): largest rank %.3g -> %.3g rows, crossing rows %.4g -> %.4g: %s\n", K, l0, l1, c0,
-                  c1, (ok1 && l1 < l0 && c1 <= 1.05 * c0) ? "kept" : "dropped");
-        if (ok1 && l1 < l0 && c1 <= 1.05 * c0) owner.swap(fine);
+        const size_t nz = ((size_t)sb + 1) << kk;
+        std::vector<double> hist((size_t)(1 << lev) * nz, 0.0);
+        for (size_t k = 0; k < T; ++k) hist[(size_t)fine[k] * nz + zof(tiles[k].P)] += (double)tlen[k];
+        std::vector<uint32_t> thr((size_t)1 << lev, 0);
+        for (int pre = 0; pre < (1 << lev); ++pre) {
+          const double *h = hist.data() + (size_t)pre * nz;
+          double tot = 0; for (size_t z = 0; z < nz; ++z) tot += h[z];
+          double acc = 0, bestd = 1e300;
+          for (size_t z = 0; z + 1 < nz; ++z) {
+            acc += h[z];
+            const double dd = std::fabs(acc - tot / 2);
+            if (dd < bestd) { bestd = dd; thr[pre] = (uint32_t)z; }
+          }
+        }
+        for (size_t k = 0; k < T; ++k) fine[k] = 2 * fine[k] + (zof(tiles[k].P) > thr[fine[k]] ? 1 : 0);
       }
+      // rows whose hop partner lives on another rank (partner tiles counted once per reading tile), largest rank
+      auto judge = [&](const std::vector<int> &own, double &crossing, double &largest) {
+        crossing = 0;
+        std::vector<double> size(nranks, 0.0);
+        for (size_t k = 0; k < T; ++k) {
+          const uint32_t P = tiles[k].P;
+          size[own[k]] += (double)tlen[k];
+          for (int b = 1; b <= p - 1; ++b)
+            if (((P >> (b - 1)) ^ (P >> b)) & 1u) {
+              const int32_t j = idx_of[P ^ (3u << (b - 1))];
+              if (j >= 0 && own[j] != own[k]) crossing += (double)tlen[j];
+            }
+        }
+        largest = 0;
+        bool empty = false;
+        for (double v : size) { largest = std::max(largest, v); if (v <= 0) empty = true; }
+        return !empty;
+      };
+      double c0 = 0, l0 = 0, c1 = 0, l1 = 0;
+      judge(owner, c0, l0);
+      const bool ok1 = judge(fine, c1, l1);
+      if (ok1 && l1 < l0 && c1 <= 1.05 * c0) owner.swap(fine);
     } else if (bm1 < 0) mode = 0;
     else {
       const uint32_t mA = (1u << bm1) - 1, mB = (1u << bm2) - 1;
@@ -653,7 +617,6 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
     }
   }
   m->shard_mode = mode;
-  tick("ownership");
 
   std::vector<int64_t> local_of(T, -1);
   m->addr.assign(nP, -1);
@@ -676,10 +639,8 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
       if (owner[k] > rank) { m->row_lo = m->row_hi = tiles[k].base; break; }
   }
 
-  tick("local tiles, addr");
   std::vector<int64_t> xcd_scratch((size_t)1 << p, -1);
   xcd_order(m, p, m->tile_prefix, m->tile_base, xcd_scratch);
-  tick("xcd_order");
 
   m->single_prefix = m->tile_prefix; m->single_base = m->tile_base;
 
@@ -855,10 +816,8 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
         if (pass == 0) ++m->n_short_multi;
       }
   }
-  tick("halo plan, length classes");
   m->tile_gbase.resize(m->tile_prefix.size());
   for (size_t k = 0; k < m->tile_prefix.size(); ++k) m->tile_gbase[k] = tile_base_global(m, m->tile_prefix[k]);
-  tick("global bases");
   return SD_OK;
 }
 
@@ -921,8 +880,6 @@ int sd_upload_model(sd_model *m, std::string &err) {
       if (m->zz_i[k] != k + 1 || m->zz_j[k] != k + 2) nn = false;
     if (nn) d.n_zz_nn = m->L - 1;
   }
-  if (getenv("SD_EXACT_DIAG")) d.diag_mode = 0;
-  if (getenv("SD_DIAG_LITERAL")) d.diag_mode = 2;
   // list-order diagonal: (J * (+-0.5)) * (+-0.5) = +-(J/4) and h * (+-0.5) = +-(h/2) exactly (binary scaling), so each term
   // of the reference's sequential sum is a sign applied to a constant: same bits, a select and an add per term
   m->zz_q.resize(m->zz_J.size());
@@ -934,16 +891,12 @@ int sd_upload_model(sd_model *m, std::string &err) {
     int ex; const double mant = std::frexp(m->hop_J[k], &ex);
     if (!(m->hop_J[k] == 0.0 || std::fabs(mant) == 0.5) || !std::isfinite(m->hop_J[k])) m->hop_pow2 = false;
   }
-  if (getenv("SD_NO_FMA")) m->hop_pow2 = false;
-  d.dbg = getenv("SD_DEBUG_SKIP") ? atoi(getenv("SD_DEBUG_SKIP")) : 0;
   int rc;
   if ((rc = up(m, m->hop_i, &d.hop_i, err))) return rc;
   if ((rc = up(m, m->hop_j, &d.hop_j, err))) return rc;
   if ((rc = up(m, m->hop_J, &d.hop_J, err))) return rc;
   if ((rc = up(m, m->zz_i, &d.zz_i, err))) return rc;
   if ((rc = up(m, m->zz_j, &d.zz_j, err))) return rc;
-  if ((rc = up(m, m->zz_J, &d.zz_J, err))) return rc;
-  if ((rc = up(m, m->field, &d.field, err))) return rc;
   if ((rc = up(m, m->zz_q, &d.zz_q, err))) return rc;
   if ((rc = up(m, m->field_h, &d.field_h, err))) return rc;
   if ((rc = up(m, m->binom, &d.binom, err))) return rc;
@@ -960,7 +913,6 @@ int sd_upload_model(sd_model *m, std::string &err) {
       if ((rc = up(m, m->suf_dg, &d.suf_dg, err))) return rc;
     } else { d.suf_part = nullptr; d.suf_dg = nullptr; }
     d.wrap_hop = m->suf_part.empty() ? -1 : m->wrap_hop; d.wrap_pb = m->wrap_pb;
-    if (getenv("SD_NO_WRAP_IMAGE")) d.wrap_hop = -1;      // A/B: the gather form of the wrap bond
     if ((rc = up(m, m->tile_gbase, &d.tile_gbase, err))) return rc;
     d.n_pack = (int)m->pack_len.size();
     if ((rc = up(m, m->pack_src, &d.pack_src, err))) return rc;

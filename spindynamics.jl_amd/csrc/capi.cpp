@@ -585,37 +585,6 @@ int sd_bench_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, void *buf_a, v
   return SD_OK;
 }
 
-// Diagnostic only (not in include/spindyn.h): runs one apply with per-tile s_memtime stamps and returns the mean
-// shader-cycle duration of each phase (prologue, list, diag+LDS, far bonds, barrier, suffix, epilogue) and the
-// mean tile lifetime.  Never used by the product path.
-int sd_debug_phase_profile(sd_ctx *ctx, sd_model *m, int dtype, void *out, const void *psi, double *phases /*8*/) {
-  if (!ctx || !m || !m->dev_ready || m->p < 0) return SD_EARG;
-  const size_t nt = m->single_prefix.size();
-  unsigned long long *d = nullptr;
-  SD_HIP(ctx, hipMalloc((void **)&d, nt * 8 * sizeof(unsigned long long)));
-  SD_HIP(ctx, hipMemset(d, 0, nt * 8 * sizeof(unsigned long long)));
-  m->dm.stamps = d;
-  sd_epi_args ea;
-  int rc = sd_launch_apply(ctx, m, dtype, out, psi, SD_EPI_PLAIN, ea);
-  m->dm.stamps = nullptr;
-  if (!rc) {
-    std::vector<unsigned long long> h(nt * 8);
-    hipError_t e = hipMemcpy(h.data(), d, nt * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = SD_EHIP;
-    for (int k = 0; k < 8; ++k) phases[k] = 0.0;
-    unsigned long long tmin = ~0ull, tmax = 0;
-    for (size_t t = 0; t < nt; ++t) {
-      for (int k = 0; k < 6; ++k) phases[k] += (double)(h[8 * t + k + 1] - h[8 * t + k]);
-      phases[6] += (double)(h[8 * t + 6] - h[8 * t]);
-      tmin = std::min(tmin, h[8 * t + 7]); tmax = std::max(tmax, h[8 * t + 7]);
-    }
-    for (int k = 0; k < 7; ++k) phases[k] /= (double)nt;
-    phases[7] = (double)(tmax - tmin) * 10.0;  // ns between first and last tile end (100 MHz realtime counter)
-  }
-  (void)hipFree(d);
-  return rc;
-}
-
 // ---- observables / initial states ("next" rows f2, f3) ----
 
 static int obs_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int what, double *out, double *q_out) {

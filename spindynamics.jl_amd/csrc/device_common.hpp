@@ -35,14 +35,8 @@ __device__ __forceinline__ double diag_of(const sd_dev_model &dm, uint64_t s) {
       anti += (int)(((s >> (dm.zz_i[k] - 1)) ^ (s >> (dm.zz_j[k] - 1))) & 1);
     return dm.diag_q * (double)(dm.n_zz - 2 * anti);
   }
+  // The reference's sum, same order, same bits: every term is +-(h_i/2) or +-(J_k/4) exactly, so it is selected, not multiplied.
   double d = 0.0;
-  if (dm.diag_mode == 2) {   // the reference's loop, literally (SD_DIAG_LITERAL; what diag_mode 0 is checked against)
-    for (int i = 1; i <= dm.L; ++i) d += dm.field[i - 1] * sz_of((s >> (i - 1)) & 1);
-    for (int k = 0; k < dm.n_zz; ++k)
-      d += (dm.zz_J[k] * sz_of((s >> (dm.zz_i[k] - 1)) & 1)) * sz_of((s >> (dm.zz_j[k] - 1)) & 1);
-    return d;
-  }
-  // Same sum, same order, same bits: every term is +-(h_i/2) or +-(J_k/4) exactly, so it is selected, not multiplied.
   // All-zero fields add +-0 to 0 and are skipped.
   if (!dm.field_zero)
     for (int i = 0; i < dm.L; ++i) { const double h = dm.field_h[i]; d += ((s >> i) & 1) ? h : -h; }

@@ -26,8 +26,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "device_common.hpp"
@@ -59,31 +57,8 @@ namespace {
 // Accumulation order per row is the reference's bond order 1..L-1.  When every
 // NN hop amplitude is a power of two (XXZChain default 0.5) J*psi is exact and
 // acc + J*psi is evaluated with one fma (bit-identical to the unfused form).
-// minimum waves per SIMD the register allocation must allow (build-time experiments: -DSD_LB_C128=6 -DSD_LB_F64=5 spill)
-#ifndef SD_SKIP_DEAD_ROWS
-#define SD_SKIP_DEAD_ROWS 1
-#endif
-#ifndef SD_SKIP_DEAD_C128
-#define SD_SKIP_DEAD_C128 0     // (round 4, wave-contiguous rows: A/B in profiles/ablation_r04.md)
-#endif
-#ifndef SD_SKIP_DEAD_C128_SHORT
-#define SD_SKIP_DEAD_C128_SHORT 1   // ... for the one-wave workgroups of the short tiles only (dilute sectors: most tiles fill one or two row groups)
-#endif
-#ifndef SD_LB_C128
-#define SD_LB_C128 4
-#endif
-#ifndef SD_LB_F64
-#define SD_LB_F64 5
-#endif
-#ifndef SD_LB_GEN
-#define SD_LB_GEN 5         // the form with the general-bond plan (GEN)
-#endif
-#ifndef SD_GEN_DEPTH
-#define SD_GEN_DEPTH 1      // register sets of its prefix-prefix streams
-#endif
-#ifndef SD_FAR_DEPTH
-#define SD_FAR_DEPTH 2      // register sets of the far-bond streams (1: no ping-pong, fewer registers, more waves)
-#endif
+// Launch bounds: minimum waves per SIMD the register allocation must allow -- 4 for ComplexF64, 5 for Float64 and for the form
+// with the general-bond plan (GEN); asking for more spills (profiles/ablation_r02.md, ablation_r03.md).
 // Rows of a thread.  A WAVE owns R*64 consecutive rows of the tile, row group r of a lane is row wave*R*64 + r*64 + lane:
 // consecutive lanes read consecutive rows (coalesced) and the R row groups of a stream differ by a compile-time byte offset
 // of r*64*sizeof(V) <= 3584, which fits the buffer instructions' 12-bit immediate -- no per-row address arithmetic.
@@ -92,8 +67,8 @@ namespace {
 // 16-byte load per row, L2/L1 resident: 64 KB for all sectors): a bond costs a shift, a mask, an LDS read and the
 // multiply-add -- the binomial form (!PK: popcount, LDS binomial look-up, two bit tests, signed offset, select) cost ~14
 // lane-operations per row and bond, half of the kernel's VALU stream (VERDICT r03, weak point 5).
-template <int NC, int R, int BLOCK, bool FMA, bool PK, bool DIAG = false, bool GEN = false>
-__global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD_LB_F64)) void k_apply_tiled(sd_dev_model dm, double *__restrict__ out_,
+template <int NC, int R, int BLOCK, bool FMA, bool PK, bool GEN = false>
+__global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_tiled(sd_dev_model dm, double *__restrict__ out_,
                                                        const double *__restrict__ psi_, int epi, sd_epi_args ea,
                                                        double *__restrict__ partials, int max_len) {
   using V = typename VT<NC>::type;
@@ -129,20 +104,8 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
   const int nn = dm.nn_hops;
   // GEN: the model's general bonds run from the host-resolved plan dm.gen (section 4b); the suffix configurations are then needed
   // for the diagonal at most
-  static_assert(!GEN || (PK && !DIAG), "general-bond plan: packed tables only");
+  static_assert(!GEN || PK, "general-bond plan: packed tables only");
   const bool need_sig = GEN ? (dm.need_sig_gen != 0) : (!PK || dm.need_sig);
-  unsigned long long *stamp = (DIAG && dm.stamps) ? dm.stamps + 8 * (size_t)tix : nullptr;
-#define SD_STAMP(k)                                                                   \
-  do {                                                                                \
-    if (DIAG && stamp) {                                                              \
-      __builtin_amdgcn_sched_barrier(0);                                              \
-      unsigned long long t__;                                                         \
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory"); \
-      __builtin_amdgcn_sched_barrier(0);                                              \
-      if (tid == 0) stamp[k] = t__;                                                   \
-    }                                                                                 \
-  } while (0)
-  SD_STAMP(0);
 
   // ---- 1. request own rows (rows >= len read 0 through the range check), the partner table and, if needed, the configurations ----
   V own[R];
@@ -181,12 +144,7 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
   if (nn > 0 && p >= 1) {
     const int b = lane + 1;
     if (b <= p) my_base = dm.far_base[(size_t)tix * (size_t)p + (size_t)lane];
-    bool fl = my_base >= 0;
-    if (DIAG) {
-      if (b <= p - 1) fl = fl && !((dm.dbg & 1) || b <= (dm.dbg >> 8));      // dbg >> 8 = m: prefix bonds 1..m left to another pass (two-pass probe)
-      else if (b == p) fl = fl && !(dm.dbg & 2);
-    }
-    fmask = __ballot(fl);
+    fmask = __ballot(my_base >= 0);
   }
   // bit p of P up:   our rows with first suffix site down (i >= nU) <-> partner rows i - nU
   // bit p of P down: our rows with first suffix site up   (i <  nU) <-> partner rows nUq + i (the shift is in the base)
@@ -202,8 +160,9 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
   // Row groups of this wave that lie wholly beyond the tile's last row issue no far-bond loads at all: their stream registers
   // stay zero.  The range check would return zeros for them anyway, but every such load still costs the address unit its
   // cycles (TA busy 70 % of the launch, ablation_r03.md section 5).
-  // Float64 only: measured -2...3 % there, but +5 % for ComplexF64 (round 3).
-  constexpr bool SKIP_DEAD = SD_SKIP_DEAD_ROWS && (NC == 1 || SD_SKIP_DEAD_C128 || (SD_SKIP_DEAD_C128_SHORT == 1 && BLOCK == 64) || (SD_SKIP_DEAD_C128_SHORT == 2 && BLOCK <= 128));
+  // Float64: measured -2...3 % there, but +5 % for ComplexF64 (round 3) -- except in the one-wave workgroups of the short tiles
+  // (dilute sectors: most tiles fill one or two row groups; profiles/ablation_r04.md).
+  constexpr bool SKIP_DEAD = NC == 1 || BLOCK == 64;
   uint32_t live = 0;
   if (SKIP_DEAD) {
 #pragma unroll
@@ -221,7 +180,6 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
       if (!SKIP_DEAD || ((live >> r) & 1u)) buf_load(v[r], rs, rel + (uint32_t)(r * 64) * ES);
   };
 
-  SD_STAMP(1);
   // first far bond in flight before the own rows have even arrived
   V va[R], vb[R];
   if (SKIP_DEAD) {
@@ -277,7 +235,6 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
       lbin[k] = (int)binom_g(dm, n, kk);
     }
 
-  SD_STAMP(2);
   // The only barrier: own rows (and binomials) are in LDS.  Placed BEFORE the far-bond streams (all waves are at the same
   // point here, their own rows have just arrived), so that afterwards every wave runs its stream and suffix phases on
   // its own clock and one wave's LDS/VALU phase overlaps its neighbours' memory phase.
@@ -286,17 +243,6 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
   // (The issues are conditional, so the compiler cannot count the loads in flight and drains them all before each
   // accumulation: the two register sets overlap less than the source suggests.  Three rewrites with counted waits -- loads
   // always issued, EMPTY bonds at the end -- were measured and lose or tie: profiles/ablation_r03.md section 3.)
-#if SD_FAR_DEPTH == 1
-  // one register set: a wave waits for each bond's rows before it asks for the next; the overlap comes from the other waves
-  // of the SIMD (the registers saved buy two more of them)
-  while (have_a) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fa.J, va[r]);
-    have_a = false;
-    if (mk) { fa = get_bond(next_lane(mk)); issue(fa, va); have_a = true; }
-  }
-  (void)fbb; (void)vb;
-#else
   while (have_a) {
     bool have_b = false;
     if (mk) { fbb = get_bond(next_lane(mk)); issue(fbb, vb); have_b = true; }
@@ -308,8 +254,6 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fbb.J, vb[r]);
   }
-#endif
-  SD_STAMP(3);
   // The packed partner table of the suffix bonds is requested only now: its 4 registers per row would otherwise be live
   // across the stream phase and cost a wave per SIMD (89 instead of 74 VGPRs for ComplexF64).  An L2 / L1 hit.
   if (PK && nn > 0) {
@@ -344,7 +288,6 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
       if (tid == 0) tile2[0] = V{};
     }
   }
-  SD_STAMP(4);
 
   // ---- general bonds (anything after the leading chain bonds: the periodic (L,1) bond, long-range lists) ----
   // Where the partner row lives follows from where the two sites are (wave-uniform per bond):
@@ -397,7 +340,7 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
   // and cost every model, with or without general bonds, a wave per SIMD)
   if (have_g && !PK) request_g0();
   // ---- 4. bonds inside the suffix ----
-  if (nn > 0 && !(DIAG && (dm.dbg & 4))) {
+  if (nn > 0) {
     if constexpr (PK) {
       // partner row + 1 from the packed table (0: no hop -> the zero row); branch-free, the R rows' LDS reads overlap
       const unsigned char *tb = reinterpret_cast<const unsigned char *>(tile);
@@ -472,13 +415,7 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
       }
       uint64_t todo = __ballot(base_k >= 0);
       int in_a = -1;                                       // the bond whose rows are in flight in va
-#if SD_GEN_DEPTH == 2
-      int in_b = -1;                                       // ... and in vb (consumed in this order)
-#endif
       if (todo) { in_a = next_lane(todo); gissue(rl64(base_k, in_a), va); }
-#if SD_GEN_DEPTH == 2
-      if (todo) { in_b = next_lane(todo); gissue(rl64(base_k, in_b), vb); }
-#endif
 #pragma nounroll
       for (int k = 0; k < nb; ++k) {
         sd_gbond gb;                                      // wave-uniform
@@ -491,14 +428,6 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
             in_a = -1;
             if (todo) { in_a = next_lane(todo); gissue(rl64(base_k, in_a), va); }
           }
-#if SD_GEN_DEPTH == 2
-          else if (k == in_b) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc[r] = accum<false>(acc[r], gb.J, vb[r]);
-            in_b = -1;
-            if (todo) { in_b = next_lane(todo); gissue(rl64(base_k, in_b), vb); }
-          }
-#endif
         } else if (gb.kind == 1) {
           // (one 4-byte word = three bonds per load: a whole 16-byte entry per row, as the chain bonds keep, would hold 16
           // registers across the streams and cost this form a wave per SIMD)
@@ -588,7 +517,6 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
     }
   }
 
-  SD_STAMP(5);
   // ---- 5. epilogue + store ----
   EpiSums sums{0.0, 0.0};
 #pragma unroll
@@ -596,8 +524,6 @@ __global__ __launch_bounds__(BLOCK, (GEN ? SD_LB_GEN : NC == 2 ? SD_LB_C128 : SD
     const int i = i0 + r * 64;
     if (i < len) epilogue<NC>(epi, ea, base + i, acc[r], tile[1 + i], out_, sums);
   }
-  SD_STAMP(6);
-  if (DIAG && stamp && tid == 0) stamp[7] = __builtin_amdgcn_s_memrealtime();
   if (epi_has_sums(epi)) {
     double a = sums.s0, b = sums.s1;
     block_reduce2(a, b, red);
@@ -1014,11 +940,7 @@ namespace {
 template <int NC, int R, int BLOCK, bool FMA, bool PK, bool GEN = false>
 int launch_tiled_cfg(sd_ctx *ctx, const sd_dev_model &dm, int nt, size_t shmem, double *out, const double *psi, int epi,
                      const sd_epi_args &ea, int max_len) {
-  // the stamped (DIAG) instantiation exists for one configuration only and is reached through sd_debug_phase_profile
-  void (*kern)(sd_dev_model, double *, const double *, int, sd_epi_args, double *, int) = k_apply_tiled<NC, R, BLOCK, FMA, PK, false, GEN>;
-  // ... and for the SD_DEBUG_SKIP timing ablations: the production instantiations carry no run-time debug branches
-  if constexpr (NC == 2 && FMA && PK && !GEN && (BLOCK == 256 || BLOCK == 128 || BLOCK == 64))
-    if (dm.stamps || dm.dbg) kern = k_apply_tiled<NC, R, BLOCK, FMA, PK, true>;
+  void (*kern)(sd_dev_model, double *, const double *, int, sd_epi_args, double *, int) = k_apply_tiled<NC, R, BLOCK, FMA, PK, GEN>;
   // per kernel AND per device, so no cache: cheap next to a launch, and only the SD_SUFFIX_BITS >= 13 tiles get here
   if (shmem > 48 * 1024)
     SD_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
@@ -1049,20 +971,14 @@ int launch_tiled(sd_ctx *ctx, const sd_dev_model &dm, int nt, int cls, size_t sh
       case 2: return launch_tiled_cfg<NC, R, 256, FMA, true, true>(ctx, dm, nt, shmem, out, psi, epi, ea, max_len);
       default: return sd_set_err(ctx, SD_EINTERNAL, "bad tile length class");
     }
-  if constexpr (NC == 1) {
-    // Float64: 8 rows per thread in workgroups of half the size (same registers as 4 ComplexF64 rows; the per-thread
-    // set-up -- far-bond list, descriptors -- is paid once per 8 rows).  SD_F64_ROWS=4 keeps 4 rows per thread.
-    static const int rows = getenv("SD_F64_ROWS") ? atoi(getenv("SD_F64_ROWS")) : 8;   // measured at L=30: 1.80 -> 1.74 ms
-    if (rows == 8 && cls >= 1 && cls <= 2)
-      switch (cls) {
-        case 1: return launch_tiled_cfg<NC, 8, 64, FMA, true>(ctx, dm, nt, shmem, out, psi, epi, ea, max_len);
-        case 2: return launch_tiled_cfg<NC, 8, 128, FMA, true>(ctx, dm, nt, shmem, out, psi, epi, ea, max_len);
-      }
-  }
-  switch (cls) {      // LS <= 12: at most C(12,6) = 924 rows, i.e. class 2
+  // LS <= 12: at most C(12,6) = 924 rows, i.e. class 2.  Float64 classes 1-2: 8 rows per thread in workgroups of half the size
+  // (same registers as 4 ComplexF64 rows; the per-thread set-up -- far-bond list, descriptors -- is paid once per 8 rows; measured
+  // at L=30: 1.80 -> 1.74 ms, profiles/r03/f64_rows.txt)
+  constexpr bool F8 = NC == 1;
+  switch (cls) {
     case 0: return launch_tiled_cfg<NC, R, 64, FMA, true>(ctx, dm, nt, shmem, out, psi, epi, ea, max_len);
-    case 1: return launch_tiled_cfg<NC, R, 128, FMA, true>(ctx, dm, nt, shmem, out, psi, epi, ea, max_len);
-    case 2: return launch_tiled_cfg<NC, R, 256, FMA, true>(ctx, dm, nt, shmem, out, psi, epi, ea, max_len);
+    case 1: return launch_tiled_cfg<NC, F8 ? 8 : R, F8 ? 64 : 128, FMA, true>(ctx, dm, nt, shmem, out, psi, epi, ea, max_len);
+    case 2: return launch_tiled_cfg<NC, F8 ? 8 : R, F8 ? 128 : 256, FMA, true>(ctx, dm, nt, shmem, out, psi, epi, ea, max_len);
   }
   return sd_set_err(ctx, SD_EINTERNAL, "bad tile length class");
 }
@@ -1076,10 +992,7 @@ int sd_launch_apply(sd_ctx *ctx, const sd_model *m, int dtype, void *out, const 
   const bool sums = (epi == SD_EPI_DOT || epi == SD_EPI_KPM || epi == SD_EPI_RESCALE_DOT);
   sd_dev_model dm = m->dm;
   sd_epi_args ea = ea_in;
-  {
-    static const int hint = getenv("SD_STREAM_HINT") ? atoi(getenv("SD_STREAM_HINT")) : 3;   // measured best: device_common.hpp, "Streams of the epilogues"
-    ea.stream_hint = hint;
-  }
+  ea.stream_hint = 3;         // measured best: device_common.hpp, "Streams of the epilogues"
   if (dm.n_local == 0) {      // a rank without rows still takes part in the reductions: its sums are zero
     if (sums) SD_HIP(ctx, hipMemsetAsync(ea.sums_dst ? ea.sums_dst : ctx->d_scalars, 0, 2 * sizeof(double), ctx->stream));
     return SD_OK;
@@ -1109,15 +1022,6 @@ int sd_launch_apply(sd_ctx *ctx, const sd_model *m, int dtype, void *out, const 
         size_t shmem = (size_t)(seg_max + 1) * esz + 16 * SD_BIN_STRIDE * sizeof(int) + 32 * sizeof(double) + 16;
         if ((dm.wrap_hop >= 0 && dm.wrap_hop == dm.nn_hops) || dm.n_gen_mixed > 0) shmem += (size_t)(m->max_tile_len_all + 1) * esz;   // the wrap bond's partner tile: any length class, owned or imported
         // (the 8-row Float64 form does not use it: launch_tiled; asking for it there would only cost occupancy -- but it is 7.4 KB)
-        {   // experiment knob: SD_LDS_MIN_KB_<cls> raises the LDS request of a class, i.e. lowers its workgroups per CU
-          static int min_kb[SD_N_LEN_CLASS] = {-1, -1, -1, -1, -1};
-          if (min_kb[cls] < 0) {
-            char name[32]; snprintf(name, sizeof(name), "SD_LDS_MIN_KB_%d", cls);
-            const char *e = getenv(name);
-            min_kb[cls] = e ? atoi(e) : 0;
-          }
-          if ((size_t)min_kb[cls] * 1024 > shmem) shmem = (size_t)min_kb[cls] * 1024;
-        }
         dm.tile_off = m->seg_off[sg];
         if (dtype == SD_C128)
           rc = m->hop_pow2 ? launch_tiled<2, true>(ctx, dm, cnt, cls, shmem, (double *)out, (const double *)psi, epi, ea, seg_max)

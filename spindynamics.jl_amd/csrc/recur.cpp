@@ -163,8 +163,7 @@ int peek_breakdown(sd_ctx *ctx, const double *d_be, int count, double tol, std::
 // Same arithmetic per element as the four-launch form; the reductions are summed in another (fixed) order.
 bool lanczos_fused_ok(const Op &op, int Qb) {
   const sd_model *m = op.m;
-  static const int on = getenv("SD_LANCZOS_FUSED") ? atoi(getenv("SD_LANCZOS_FUSED")) : 1;
-  return on && m->nranks == 1 && !op.ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 4096 && op.n <= ((int64_t)1 << 22) &&
+  return m->nranks == 1 && !op.ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 4096 && op.n <= ((int64_t)1 << 22) &&
          (int64_t)Qb * op.n * 16 * 3 <= ((int64_t)4 << 30);
 }
 int lanczos_fused(Op &op, int Qb, double *u0, int mm, int form, int negate, double tol, std::vector<double> &alpha,
@@ -221,9 +220,6 @@ int extremal_dev(Op &op, int lanc_m, double tol, double *v_prev, int negate, dou
   const int64_t N = op.n;
   const int mm = (int)std::min<int64_t>(lanc_m, op.m->N);
   if (mm < 1) return sd_set_err(ctx, SD_EARG, "lanc_m must be >= 1");
-  DBuf w, vc;
-  RC(w.alloc(ctx, 2 * N)); RC(vc.alloc(ctx, 2 * N));
-  double *v_curr = vc.p;
   int rc = 0;
   double nrm = norm_dev(op, v_prev, 2 * N, &rc); RC(rc);
   RC(sd_k_scale_div(ctx, v_prev, v_prev, 2 * N, nrm));                     // :40
@@ -241,12 +237,13 @@ int extremal_dev(Op &op, int lanc_m, double tol, double *v_prev, int negate, dou
   }
   // the loop is queued without host round trips (alpha_j, beta_j stay on the device, see tridiag_dev); the break on
   // beta_j < tol (:66-70) is applied to the values read back at the end.  Vectors stay un-normalised (k_lanczos_fold).
-  DBuf ab; RC(ab.alloc(ctx, 4 * (int64_t)mm + 2));
+  DBuf w, vc, ab;
+  RC(w.alloc(ctx, 2 * N)); RC(vc.alloc(ctx, 2 * N)); RC(ab.alloc(ctx, 4 * (int64_t)mm + 2));
   double *d_al = ab.p, *d_be = ab.p + mm, *d_n2 = ab.p + 2 * (int64_t)mm;      // d_n2[2j]: |w_j|^2
   SD_HIP(ctx, hipMemsetAsync(ab.p, 0, sizeof(double) * (4 * (size_t)mm + 2), ctx->stream));
   sd_epi_args ea; ea.negate = negate;
   std::vector<double> peek;
-  double *ucur = v_prev, *uprev = v_curr, *t = w.p;
+  double *ucur = v_prev, *uprev = vc.p, *t = w.p;
   const double *n2c = nullptr, *n2p = nullptr;       // |ucur|^2, |uprev|^2 on the device; null: normalised
   for (int j = 1; j <= mm; ++j) {
     RC(op.apply(SD_C128, t, ucur, SD_EPI_DOT, ea));                        // :51 + :55 fused -> d_scalars[0]
@@ -795,8 +792,7 @@ static int sd_lanczos_groundstate_impl(sd_ctx *ctx, const sd_model *m, int lanc_
     }
     return SD_OK;
   };
-  static const int gs_fused_env = getenv("SD_GS_FUSED") ? atoi(getenv("SD_GS_FUSED")) : 1;
-  if (ctx->gs_blocked && !ctx->user_apply && gs_fused_env && mm >= 2) {
+  if (ctx->gs_blocked && !ctx->user_apply && mm >= 2) {
     // Passes that sum their producer's partial lists themselves (kernels_blas1.hip, k_gs_*): a step is the apply, one launch per
     // block of 8 columns, the update and the normalising pass -- no reduction launches, alpha_j and beta_j stay on the device --
     // and the orthogonality check of step j rides along with the Gram-Schmidt passes of step j + 1 (they read the same columns;

@@ -99,19 +99,16 @@ struct sd_dev_model {
   int64_t fs_halo_off[SD_FS_MAX_RANKS];   // per peer rank: element offset of its slab in the halo buffer, -1: nothing imported from it
   int64_t fs_peer_lo[SD_FS_MAX_RANKS];    // per peer rank: first row (of the peer's local vector) held by that slab
   int nn_hops;           // leading hops that are exactly (1,2),(2,3),...,(L-1,L) in order (L-1 or 0)
-  int diag_mode;         // 0 list order with exact term magnitudes (select + add per term), 1 uniform closed form, 2 literal reference loop (SD_DIAG_LITERAL)
+  int diag_mode;         // 0 list order with exact term magnitudes (select + add per term), 1 uniform closed form
   double diag_q;         // Jz/4 for diag_mode 1
   int n_zz_nn;           // leading zz bonds that are the NN chain in order (L-1 or 0), for diag_mode 1
   int field_zero;
-  int dbg;               // timing-only ablation bits from env SD_DEBUG_SKIP (1 prefix bonds, 2 straddle, 4 suffix bonds)
   int64_t N;             // global dimension
   int64_t n_local;       // rows owned by this shard (== N unsharded)
   int64_t row_lo;        // first owned global row
   const int *hop_i, *hop_j;      // 1-based sites
   const double *hop_J;
   const int *zz_i, *zz_j;
-  const double *zz_J;
-  const double *field;
   const double *zz_q;            // (zz_J * 0.5) * 0.5: the exact magnitude of every zz term (diag_mode 0)
   const double *field_h;         // field * 0.5: the exact magnitude of every field term
   const double *diag_cache;      // list-order diagonal of every local row, computed once (tiled plans without an exact shortcut), or null
@@ -130,11 +127,13 @@ struct sd_dev_model {
   const uint16_t *suf_rank;      // 2^LS entries: rank of sigma inside its sector
   // Packed partner table of the suffix bonds (LS <= 12), one 16-byte entry per row of every suffix sector, indexed like
   // suf_states: word w holds three 10-bit fields, field 3*w + j (bits 10j..10j+9) = 1 + (row of the hop partner on suffix bond
-  // a = 3*w + j + 1 inside the tile), 0 when the bond cannot flip.  Word 3 also carries, above its two bond fields, the number of
-  // anti-parallel neighbour pairs INSIDE the suffix (bits 20..23) and the first suffix site (bit 30): with them the uniform-zz
-  // diagonal needs no configuration at all.  Null for LS > 12 (k_apply_tiled then computes partners from binomials).
+  // a = 3*w + j + 1 inside the tile), 0 when the bond cannot flip.  Word 3 holds the fields of bonds 10 and 11 in bits 0..19 and,
+  // with a wrap bond (wrap_hop below), that bond's partner row in bits 20..29 and the row's suffix site of it in bit 30.  Null for
+  // LS > 12 (k_apply_tiled then computes partners from binomials).
   const uint32_t *suf_part;
-  const uint8_t *suf_dg;         // per row of every suffix sector: anti-parallel pairs inside the suffix (bits 0..3), first suffix site (bit 4); with suf_part
+  // per row of every suffix sector: anti-parallel neighbour pairs inside the suffix (bits 0..3) and the first suffix site (bit 4):
+  // with them the uniform-zz diagonal needs no configuration at all; with suf_part
+  const uint8_t *suf_dg;
   // First general bond of the hop list when it joins a prefix site and a suffix site (the periodic chain's (L, 1)): every partner
   // row lies in the ONE tile P ^ (1 << wrap_pb).  suf_part's word 3 then holds, in bits 20..29, 1 + the partner's row inside that
   // tile (suffix sector t' + 1 when the row's suffix site is down, t' - 1 when it is up) and in bit 30 the row's suffix site; the
@@ -148,7 +147,6 @@ struct sd_dev_model {
   const uint32_t *single_prefix; // the local tiles in launch order (k_apply_tiled)
   const int64_t *single_base;
   const sd_tile_rec *single_rec;
-  unsigned long long *stamps;    // diagnostic builds only (sd_debug_phase_profile): 8 s_memtime stamps per tile, else null
   // General bonds of a tiled plan with the packed tables (LS <= 12), resolved on the host: n_gen = n_hop - nn_hops entries in list
   // order, or 0 (no plan: k_apply_tiled then looks every general partner up per row).  gen_ss_part: per chunk of 12 suffix-suffix
   // bonds one 16-byte entry per row of every suffix sector (chunk-major), 10-bit fields like suf_part.  mix_part: per suffix
@@ -249,7 +247,7 @@ struct sd_epi_args {
   void *accv = nullptr;         // psi_t (CHEB)
   const void *phi = nullptr;    // KPM reference vector
   int negate = 0;               // PLAIN / DOT: out = -(H psi); batched launches: bit k = vector k
-  int stream_hint = 0;          // set by sd_launch_apply: bit 0 non-temporal stores of out, bit 1 non-temporal side streams (prev, phi, psi_t); env SD_STREAM_HINT
+  int stream_hint = 0;          // set by sd_launch_apply: bit 0 non-temporal stores of out, bit 1 non-temporal side streams (prev, phi, psi_t)
   double *sums_dst = nullptr;   // where the two reduced sums of a DOT / KPM / RESCALE_DOT epilogue go (device; null: ctx->d_scalars[0..1])
   const void *halo = nullptr;   // sharded plans: imported partner tiles (offsets >= n_local); null = halo follows psi's owned rows
   // Batched launch (k_apply_tiled, unsharded tiled plans): grid.y = batch vectors stored `bstride` ELEMENTS apart -- psi, out,

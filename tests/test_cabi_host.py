@@ -419,3 +419,28 @@ def test_bench_helpers_hash_and_cores(tmp_path, monkeypatch):
     assert bench.kernel_source_hash() != h0
     use, aff, quota = bench.host_cores()
     assert 1 <= use <= aff and (quota is None or quota > 0)
+
+
+LIBRARY_ENV = {
+    "SD_SUFFIX_BITS", "SD_LEN_CLASSES", "SD_SHORT_TILES", "SD_GEN_PLAN",          # tiling and plan
+    "SD_DIAG_CACHE", "SD_OBS_CHUNKED", "SD_SZQ_FULL_GENERIC",                     # kernel paths
+    "SD_SHARD_PACK", "SD_SHARD_MODE",                                             # sharding
+    "SD_Q_BATCH", "SD_POOL_MAX_GB", "SD_POOL_DEBUG",                              # context defaults
+    "SD_XFER", "SD_XFER_THREADS", "SD_XFER_CHUNK_MB", "SD_XFER_MIN_MB",           # host <-> device copies
+}
+
+
+def test_library_reads_only_the_documented_environment():
+    """The environment variables libspindyn reads are exactly the documented set: an A/B switch
+    added for an experiment shows up here instead of staying in the library unnoticed."""
+    csrc = os.path.join(ROOT, "spindynamics.jl_amd", "csrc")
+    names, other = set(), []
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".cpp", ".hip", ".hpp")):
+            continue
+        src = open(os.path.join(csrc, fn)).read()
+        names |= set(re.findall(r'\b(?:getenv|env_mb)\(\s*"(SD_[A-Z0-9_]+)"', src))
+        # a name built at run time would escape the list above; the one such read is env_mb's own
+        other += [(fn, a) for a in re.findall(r'\bgetenv\(\s*([^")\s][^)]*)\)', src)]
+    assert other == [("xfer.cpp", "name")], other
+    assert names == LIBRARY_ENV, (sorted(names - LIBRARY_ENV), sorted(LIBRARY_ENV - names))
