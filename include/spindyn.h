@@ -234,6 +234,30 @@ int sd_spectral_from_tridiagonal(const double *alpha, const double *beta, int m,
 int sd_lanczos_sqw(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n,
                    const double *q, int Qn, const double *omega, int W, int lanc_m, double eta, int broaden,
                    double *Smat_out);
+/* Transverse S(q,w) between adjacent sectors.  src holds psi0 (sector nup); dst is the sector the operator maps it to:
+ * op SD_SPIN_MINUS, S^-_q = L^(-1/2) sum_r e^{iqr} S^-_{r+1}, needs dst.nup == src.nup - 1 (S^{+-}); op SD_SPIN_PLUS, S^+_q,
+ * needs dst.nup == src.nup + 1 (S^{-+}).  Two full-basis models of the same L pair up too (dst may be src).  The caller owns
+ * both models; they must have the same L and bit-identical hop, zz and field lists, neither may be sharded, and the context
+ * may not hold a caller's operator (it belongs to one sector): any mismatch is SD_EARG, sd_last_error names it.
+ * sd_spm_q: phi_out (n_dst = dst's dimension, always ComplexF64) = S^-+_q psi0 (n_src = src's dimension, dtype_in).  The
+ * rounding is fixed: per target row the terms r = 0..L-1 in ascending order, acc += (c_r x.re - s_r x.im, c_r x.im + s_r x.re)
+ * without fused multiply-adds, out = acc / sqrt(L) as (nf acc.re, nf acc.im).  Wrong lengths are SD_EDIM.
+ * sd_spm_q_dev: the same on device vectors, ordered on the context's stream. */
+int sd_spm_q(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0_host,
+             int64_t n_src, double q, void *phi_out_host, int64_t n_dst);
+int sd_spm_q_dev(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0_dev,
+                 int64_t n_src, double q, void *phi_out_dev, int64_t n_dst);
+/* kpm_sqw / lanczos_sqw with phi = S^-+_q psi0 in place of S^z_q psi0 (S^{+-} for SD_SPIN_MINUS, S^{-+} for SD_SPIN_PLUS).
+ * psi0 has n = src's dimension; E0 comes from src (kpm: <psi0|H psi0>; lanczos: Re sum psi_i (H psi)_i, as sd_lanczos_sqw);
+ * the recursion -- bounds (have_ab == 0: two 80-step Lanczos runs keyed by `seed`), moments, tridiagonal -- runs on dst's H.
+ * Normalisation, zero-norm rows, kernels and the |phi|^2 scaling are those of sd_kpm_sqw / sd_lanczos_sqw.  Errors as
+ * sd_spm_q. */
+int sd_kpm_sqw_transverse(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype, const void *psi0_host,
+                          int64_t n, const double *q, int Qn, const double *omega, int W, int have_ab, double a, double b,
+                          int kpm_m, int kernel, uint64_t seed, double *Smat_out);
+int sd_lanczos_sqw_transverse(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype, const void *psi0_host,
+                              int64_t n, const double *q, int Qn, const double *omega, int W, int lanc_m, double eta,
+                              int broaden, double *Smat_out);
 
 /* ---- observables and initial states (reference src/Observables.jl, src/InitialStates.jl) ---- */
 /* magnetization_per_site   src/Observables.jl:14-36 : mags_out[L] = <S^z_i> */

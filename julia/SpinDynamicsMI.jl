@@ -268,13 +268,54 @@ function time_evolve(model::Model, ψ0::AbstractVector, t::Real; method::Symbol=
     throw(ArgumentError("unsupported time-evolution method: $method"))
 end
 
+# The sector S^-_q (op 2) or S^+_q (op 1) maps model's sector to: the model itself for the full basis, nothing when there is none.
+function transverse_target(model::Model, op::Int)
+    model.nup === nothing && return model
+    t = model.nup + (op == 2 ? -1 : 1)
+    (t < 0 || t > model.L) && return nothing
+    return build_model(model.L; nup=t, hopping=model.hopping_list, onsite_field=model.onsite_field, zz=model.zz_list)
+end
+
+# S^{+-} (op 2), S^{-+} (op 1) as (W x Qn) column-major: sd_kpm_sqw_transverse / sd_lanczos_sqw_transverse on the adjacent sector
+function transverse_rows(model::Model, x, q_list, ω_range, op::Int, method::Symbol, lanc_m, eta, br, have, a, b, kpm_m, kern, seed)
+    S = zeros(Float64, length(ω_range), length(q_list))
+    dst = transverse_target(model, op)
+    dst === nothing && return S                                        # no target sector: phi = 0, zero rows
+    if method === :lanczos
+        check(ccall((:sd_lanczos_sqw_transverse, libspindyn), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Int64, Ptr{Float64}, Cint, Ptr{Float64}, Cint, Cint,
+                     Float64, Cint, Ptr{Float64}),
+                    model.ctx.h, model.h, dst.h, op, dtype_code(eltype(x)), x, length(x), q_list, length(q_list), ω_range,
+                    length(ω_range), lanc_m, eta, br, S), model.ctx.h)
+    else
+        check(ccall((:sd_kpm_sqw_transverse, libspindyn), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Int64, Ptr{Float64}, Cint, Ptr{Float64}, Cint, Cint,
+                     Float64, Float64, Cint, Cint, UInt64, Ptr{Float64}),
+                    model.ctx.h, model.h, dst.h, op, dtype_code(eltype(x)), x, length(x), q_list, length(q_list), ω_range,
+                    length(ω_range), have, have ? a : 0.0, have ? b : 0.0, kpm_m, kern, seed, S), model.ctx.h)
+    end
+    return S
+end
+
 function dynamical_structure_factor(model::Model, ψ0::AbstractVector, q::AbstractVector, ω::AbstractVector;
-                                    method::Symbol=:lanczos, lanc_m::Int=200, eta::Float64=0.05, broaden::Symbol=:lorentz,
-                                    a::Union{Nothing,Float64}=nothing, b::Union{Nothing,Float64}=nothing,
+                                    method::Symbol=:lanczos, component::Symbol=:zz, lanc_m::Int=200, eta::Float64=0.05,
+                                    broaden::Symbol=:lorentz, a::Union{Nothing,Float64}=nothing, b::Union{Nothing,Float64}=nothing,
                                     kpm_m::Int=200, kernel::Symbol=:jackson, seed::Integer=0)
     q_list = Float64.(q); ω_range = Float64.(ω)
     x = eltype(ψ0) <: Complex ? Vector{ComplexF64}(ψ0) : Vector{Float64}(ψ0)
     S = Matrix{Float64}(undef, length(ω_range), length(q_list))      # C row-major (Qn x W) == Julia (W x Qn) column-major
+    if component !== :zz
+        # transverse spectra: S^{+-} (:pm), S^{-+} (:mp), S^{xx} = S^{yy} = (S^{+-} + S^{-+}) / 4 (:xx)
+        ops = component === :pm ? (2,) : component === :mp ? (1,) : component === :xx ? (2, 1) :
+              throw(ArgumentError("unknown component: $component; expected :zz, :pm, :mp or :xx"))
+        (method === :lanczos || method === :kpm) || throw(ArgumentError("unsupported dynamical structure-factor method: $method"))
+        br = broaden === :lorentz ? 0 : broaden === :gauss ? 1 : error("unknown broadening: $broaden")
+        have = a !== nothing && b !== nothing
+        kern = kernel === :jackson ? 0 : kernel === :lorentz ? 1 : 2
+        parts = [transverse_rows(model, x, q_list, ω_range, op, method, lanc_m, eta, br, have, a, b, kpm_m, kern, seed) for op in ops]
+        S = length(parts) == 2 ? 0.25 .* (parts[1] .+ parts[2]) : parts[1]
+        return permutedims(S)
+    end
     if method === :lanczos
         br = broaden === :lorentz ? 0 : broaden === :gauss ? 1 : error("unknown broadening: $broaden")
         check(ccall((:sd_lanczos_sqw, libspindyn), Cint,

@@ -129,6 +129,10 @@ PROTOTYPES = {
     "sd_kpm_sqw": (_i, [_vp, _vp, _i, _vp, _i64, _dp, _i, _dp, _i, _i, _d, _d, _i, _i, _u64, _dp]),
     "sd_spectral_from_tridiagonal": (_i, [_dp, _dp, _i, _d, _d, _dp, _i, _d, _i, _dp]),
     "sd_lanczos_sqw": (_i, [_vp, _vp, _i, _vp, _i64, _dp, _i, _dp, _i, _i, _d, _i, _dp]),
+    "sd_spm_q": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _d, _vp, _i64]),
+    "sd_spm_q_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _d, _vp, _i64]),
+    "sd_kpm_sqw_transverse": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _dp, _i, _dp, _i, _i, _d, _d, _i, _i, _u64, _dp]),
+    "sd_lanczos_sqw_transverse": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _dp, _i, _dp, _i, _i, _d, _i, _dp]),
     "sd_magnetization": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),
     "sd_magnetization_dev": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),
     "sd_connected_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),

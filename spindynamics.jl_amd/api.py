@@ -49,11 +49,20 @@ def structure_factor(model, psi):
     return structure_factor_Sq(psi, model)
 
 
-def dynamical_structure_factor(model, psi0, q, omega, method="lanczos", **kwargs):
+def dynamical_structure_factor(model, psi0, q, omega, method="lanczos", component="zz", **kwargs):
     """dynamical_structure_factor(model, psi0, q, omega; method=:lanczos, kwargs...) -> S[len(q), len(omega)]
-    -- src/PublicAPI.jl:122-155"""
+    -- src/PublicAPI.jl:122-155.  component="zz" is S^zz; "+-", "-+" and "xx" are the transverse spectra of
+    solvers.lanczos_sqw_transverse / kpm_sqw_transverse (intermediate states in the adjacent sectors)."""
     q_list = np.asarray(q, dtype=np.float64)
     w = np.asarray(omega, dtype=np.float64)
+    if component != "zz":
+        if component not in ("+-", "-+", "xx"):
+            raise ArgumentError(f"unknown component: {component}; expected \"zz\", \"+-\", \"-+\" or \"xx\"")
+        if method == "lanczos":
+            return solvers.lanczos_sqw_transverse(psi0, model, q_list, w, component=component, **kwargs)
+        if method == "kpm":
+            return solvers.kpm_sqw_transverse(psi0, model, q_list, w, component=component, **kwargs)
+        raise ArgumentError(f"unsupported dynamical structure-factor method: {method}")
     if method == "lanczos":
         return solvers.lanczos_sqw(psi0, model, q_list, w, **kwargs)
     if method == "kpm":

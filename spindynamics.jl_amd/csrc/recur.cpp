@@ -1411,3 +1411,174 @@ extern "C" int sd_lanczos_sqw(sd_ctx *ctx, const sd_model *m, int dtype, const v
                               int Qn, const double *omega, int W, int lanc_m, double eta, int broaden, double *Smat) {
   SD_ABI_GUARD(ctx, sd_lanczos_sqw_impl(ctx, m, dtype, psi0, n, q, Qn, omega, W, lanc_m, eta, broaden, Smat));
 }
+
+// ---- transverse S(q,w): S^+- and S^-+ between adjacent sectors (DESIGN.md "Transverse S(q,w)") ----
+// The caller owns both models: src holds psi0, dst is the sector S^-_q (op SD_SPIN_MINUS) or S^+_q (SD_SPIN_PLUS) maps it to.
+// E0 comes from src, the recursion (bounds, moments, tridiagonal) runs on dst's H.
+namespace {
+template <class T>
+bool same_bits(const std::vector<T> &x, const std::vector<T> &y) {
+  return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), sizeof(T) * x.size()) == 0);
+}
+int spm_check(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op) {
+  if (!ctx) return SD_EARG;
+  if (!src || !dst) return sd_set_err(ctx, SD_EARG, "null model");
+  if (op != SD_SPIN_MINUS && op != SD_SPIN_PLUS) return sd_set_err(ctx, SD_EARG, "op must be SD_SPIN_MINUS or SD_SPIN_PLUS");
+  if (src->L != dst->L) return sd_set_err(ctx, SD_EARG, "source and target models have different L");
+  if (!same_bits(src->hop_i, dst->hop_i) || !same_bits(src->hop_j, dst->hop_j) || !same_bits(src->hop_J, dst->hop_J))
+    return sd_set_err(ctx, SD_EARG, "source and target models have different hopping lists");
+  if (!same_bits(src->zz_i, dst->zz_i) || !same_bits(src->zz_j, dst->zz_j) || !same_bits(src->zz_J, dst->zz_J))
+    return sd_set_err(ctx, SD_EARG, "source and target models have different zz lists");
+  if (!same_bits(src->field, dst->field)) return sd_set_err(ctx, SD_EARG, "source and target models have different fields");
+  if ((src->nup < 0) != (dst->nup < 0)) return sd_set_err(ctx, SD_EARG, "one model is a sector, the other the full basis");
+  if (src->nup >= 0 && dst->nup != src->nup + (op == SD_SPIN_MINUS ? -1 : 1))
+    return sd_set_err(ctx, SD_EARG, op == SD_SPIN_MINUS ? "target nup must be source nup - 1 for S^-" : "target nup must be source nup + 1 for S^+");
+  if (src->nranks != 1 || dst->nranks != 1) return sd_set_err(ctx, SD_EARG, "transverse operators need unsharded models");
+  if (ctx->user_apply) return sd_set_err(ctx, SD_EARG, "a caller's operator is installed on this context: it belongs to one sector");
+  if (!src->dev_ready || !dst->dev_ready) return sd_set_err(ctx, SD_EARG, "model has no device tables (created without a context)");
+  return SD_OK;
+}
+
+// the source sector's part of the S(q,w) drivers: psi0 promoted to ComplexF64 on the device (psic, 2 n doubles) and the
+// unconjugated sum Re sum psi_i (H psi)_i (lanczos) or <psi0|H psi0> (kpm), as the zz drivers form them
+int transverse_source(Op &os, int dtype, const void *psi0, int64_t n, bool lanczos, DBuf &psic, double *E0) {
+  sd_ctx *ctx = os.ctx;
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  RC(psic.alloc(ctx, 2 * n));
+  DBuf in, tmp;
+  RC(in.alloc(ctx, nc * n));
+  RC(h2d(ctx, in.p, psi0, nc * n));
+  RC(sd_k_promote(ctx, psic.p, in.p, nc, n));
+  in.release();
+  RC(tmp.alloc(ctx, 2 * n));
+  double s[2];
+  if (lanczos) {
+    RC(plain_op(ctx, os.m, SD_C128, tmp.p, psic.p));                                      // src/LanczosSqw.jl:58-59
+    RC(sd_k_dotu(ctx, psic.p, tmp.p, n, 4));
+    RC(sd_read_scalars(ctx, 4, 2, s));
+  } else {
+    sd_epi_args ea;
+    RC(os.apply(SD_C128, tmp.p, psic.p, SD_EPI_DOT, ea));                                 // src/KPM_Sqw.jl:208-209
+    RC(sd_read_scalars(ctx, 0, 2, s));
+  }
+  *E0 = s[0];
+  return SD_OK;
+}
+}  // namespace
+
+static int sd_spm_q_impl(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0,
+                         int64_t n_src, double q, void *phi, int64_t n_dst, bool on_dev) {
+  RC(spm_check(ctx, src, dst, op));
+  if (!psi0 || !phi) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (dtype_in != SD_F64 && dtype_in != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (n_src != src->N) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the source basis dimension");
+  if (n_dst != dst->N) return sd_set_err(ctx, SD_EDIM, "output length does not match the target basis dimension");
+  SD_HIP(ctx, hipSetDevice(ctx->device));
+  if (on_dev) return sd_launch_spm_q(ctx, src, dst, op, dtype_in, psi0, q, phi);
+  const int nc = dtype_in == SD_C128 ? 2 : 1;
+  DBuf in, out;
+  RC(in.alloc(ctx, nc * n_src)); RC(out.alloc(ctx, 2 * n_dst));
+  RC(h2d(ctx, in.p, psi0, nc * n_src));
+  RC(sd_launch_spm_q(ctx, src, dst, op, dtype_in, in.p, q, out.p));
+  return d2h(ctx, phi, out.p, 2 * n_dst);
+}
+extern "C" int sd_spm_q(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0_host,
+                        int64_t n_src, double q, void *phi_out_host, int64_t n_dst) {
+  SD_ABI_GUARD(ctx, sd_spm_q_impl(ctx, src, dst, op, dtype_in, psi0_host, n_src, q, phi_out_host, n_dst, false));
+}
+extern "C" int sd_spm_q_dev(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0_dev,
+                            int64_t n_src, double q, void *phi_out_dev, int64_t n_dst) {
+  SD_ABI_GUARD(ctx, sd_spm_q_impl(ctx, src, dst, op, dtype_in, psi0_dev, n_src, q, phi_out_dev, n_dst, true));
+}
+
+// kpm_sqw with phi = S^-+_q psi0: the loop of kpm_sqw_core's one-momentum-at-a-time path, the recursion on dst
+static int sd_kpm_sqw_transverse_impl(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype, const void *psi0,
+                                      int64_t n, const double *q, int Qn, const double *omega, int W, int have_ab, double a,
+                                      double b, int kpm_m, int kernel, uint64_t seed, double *Smat) {
+  RC(spm_check(ctx, src, dst, op));
+  Op os; RC(os.init(ctx, src, nullptr));
+  Op od; RC(od.init(ctx, dst, nullptr));
+  if (n != src->N) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the source basis dimension");
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (kpm_m < 2) return sd_set_err(ctx, SD_EARG, "kpm_m must be >= 2");
+  if (!psi0 || !Smat || (Qn > 0 && !q) || (W > 0 && !omega)) return sd_set_err(ctx, SD_EARG, "null argument");
+  const int64_t nd = dst->N;
+  DBuf psic, phi;
+  double E0 = 0.0;
+  RC(transverse_source(os, dtype, psi0, n, false, psic, &E0));
+  if (!have_ab) {                                                                         // the target sector's bounds
+    double Emin, Emax;
+    RC(energy_bounds_core(od, 80, nullptr, nullptr, true, seed, &Emin, &Emax));
+    sd_kpm_rescaling_from_bounds(Emin, Emax, &a, &b);
+  }
+  std::vector<double> mu(kpm_m), g(kpm_m);
+  sd_kpm_kernel(kpm_m, kernel, g.data());
+  std::vector<int> same_as;   // H is real in both sectors: phi_{2pi-q} = conj(phi_q) for a real psi0
+  RC(pair_momenta(os, dtype, psic.p, n, q, Qn, same_as));
+  RC(phi.alloc(ctx, 2 * nd));
+  int rc = 0;
+  for (int iq = 0; iq < Qn; ++iq) {
+    double *Srow = Smat + (size_t)iq * W;
+    if (same_as[iq] >= 0) { std::memcpy(Srow, Smat + (size_t)same_as[iq] * W, sizeof(double) * (size_t)W); continue; }
+    RC(sd_launch_spm_q(ctx, src, dst, op, SD_C128, psic.p, q[iq], phi.p));
+    const double norm_phi = norm_dev(od, phi.p, 2 * nd, &rc); RC(rc);
+    if (norm_phi == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }       // src/KPM_Sqw.jl:226-229
+    RC(sd_k_scale_div(ctx, phi.p, phi.p, 2 * nd, norm_phi));
+    RC(moments_dev(od, phi.p, kpm_m, a, b, mu.data()));
+    for (int k = 0; k < kpm_m; ++k) mu[k] *= g[k];
+    sd_kpm_reconstruct(mu.data(), kpm_m, omega, W, a, b, E0, Srow);
+    const double n2 = norm_phi * norm_phi;
+    for (int iw = 0; iw < W; ++iw) Srow[iw] *= n2;
+  }
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+extern "C" int sd_kpm_sqw_transverse(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype, const void *psi0,
+                                     int64_t n, const double *q, int Qn, const double *omega, int W, int have_ab, double a,
+                                     double b, int kpm_m, int kernel, uint64_t seed, double *Smat) {
+  SD_ABI_GUARD(ctx, sd_kpm_sqw_transverse_impl(ctx, src, dst, op, dtype, psi0, n, q, Qn, omega, W, have_ab, a, b, kpm_m, kernel,
+                                               seed, Smat));
+}
+
+// lanczos_sqw with phi = S^-+_q psi0: the loop of sd_lanczos_sqw_impl's one-momentum-at-a-time path, the recursion on dst
+static int sd_lanczos_sqw_transverse_impl(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype,
+                                          const void *psi0, int64_t n, const double *q, int Qn, const double *omega, int W,
+                                          int lanc_m, double eta, int broaden, double *Smat) {
+  RC(spm_check(ctx, src, dst, op));
+  Op os; RC(os.init(ctx, src, nullptr));
+  Op od; RC(od.init(ctx, dst, nullptr));
+  if (n != src->N) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the source basis dimension");
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (broaden != SD_BROADEN_LORENTZ && broaden != SD_BROADEN_GAUSS) return sd_set_err(ctx, SD_EARG, "unknown broadening");
+  if (lanc_m < 1) return sd_set_err(ctx, SD_EARG, "lanc_m must be >= 1");
+  if (!psi0 || !Smat || (Qn > 0 && !q) || (W > 0 && !omega)) return sd_set_err(ctx, SD_EARG, "null argument");
+  const int64_t nd = dst->N;
+  DBuf psic, phi;
+  double E0 = 0.0;
+  RC(transverse_source(os, dtype, psi0, n, true, psic, &E0));
+  const int mm = (int)std::max<int64_t>(std::min<int64_t>(lanc_m, nd), 1);
+  std::vector<double> alpha(mm), beta(mm);
+  std::vector<int> same_as;
+  RC(pair_momenta(os, dtype, psic.p, n, q, Qn, same_as));
+  RC(phi.alloc(ctx, 2 * nd));
+  int rc = 0;
+  for (int iq = 0; iq < Qn; ++iq) {
+    double *Srow = Smat + (size_t)iq * W;
+    if (same_as[iq] >= 0) { std::memcpy(Srow, Smat + (size_t)same_as[iq] * W, sizeof(double) * (size_t)W); continue; }
+    RC(sd_launch_spm_q(ctx, src, dst, op, SD_C128, psic.p, q[iq], phi.p));
+    const double normv = norm_dev(od, phi.p, 2 * nd, &rc); RC(rc);
+    if (normv == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }          // src/LanczosSqw.jl:67-70
+    RC(sd_k_scale_div(ctx, phi.p, phi.p, 2 * nd, normv));
+    int m_eff = 0;
+    RC(tridiag_dev(od, phi.p, lanc_m, 1e-12, alpha.data(), beta.data(), &m_eff));
+    int rs = sd_spectral_from_tridiagonal(alpha.data(), beta.data(), m_eff, normv, E0, omega, W, eta, broaden, Srow);
+    if (rs) return sd_set_err(ctx, rs, "spectral_from_tridiagonal failed");
+  }
+  return SD_OK;
+}
+extern "C" int sd_lanczos_sqw_transverse(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype,
+                                         const void *psi0, int64_t n, const double *q, int Qn, const double *omega, int W,
+                                         int lanc_m, double eta, int broaden, double *Smat) {
+  SD_ABI_GUARD(ctx, sd_lanczos_sqw_transverse_impl(ctx, src, dst, op, dtype, psi0, n, q, Qn, omega, W, lanc_m, eta, broaden,
+                                                   Smat));
+}

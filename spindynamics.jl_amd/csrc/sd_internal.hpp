@@ -271,6 +271,9 @@ int sd_launch_pack(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, v
 int sd_launch_fill_randn_local(sd_ctx *ctx, const sd_model *m, int dtype, void *x, uint64_t seed);
 int sd_launch_spin_op(sd_ctx *ctx, const sd_model *m, int dtype, int site, int op, const void *psi, void *out);
 int sd_launch_szq(sd_ctx *ctx, const sd_model *m, int dtype_in, const void *psi0, double q, void *phi);
+// phi (dst's rows, ComplexF64) = S^-_q psi0 (op SD_SPIN_MINUS) or S^+_q psi0 (SD_SPIN_PLUS) with psi0 on src's rows (kernels_transverse.hip)
+int sd_launch_spm_q(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0, double q,
+                    void *phi);
 
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a

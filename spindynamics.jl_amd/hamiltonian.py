@@ -114,6 +114,53 @@ def Sz_q_vector(model, psi0, q):
     return phi
 
 
+def _transverse_target(model, op):
+    """The sector S^-_q (op SD_SPIN_MINUS = 2) or S^+_q (SD_SPIN_PLUS = 1) maps `model`'s sector to: the model itself for the
+    full basis, None when there is none (nup = 0 for S^-, nup = L for S^+)."""
+    if model.nup is None:
+        return model
+    t = model.nup + (-1 if op == 2 else 1)
+    if t < 0 or t > model.L:
+        return None
+    return model.adjacent_sector(t - model.nup)
+
+
+def _spm_q_vector(model, psi0, q, op):
+    if len(psi0) != model.N:
+        raise DimensionMismatch(f"psi0 has length {len(psi0)}, expected {model.N}")
+    dst = _transverse_target(model, op)
+    ctx = model.ctx
+    if _is_torch(psi0):
+        import torch
+        code = _dtype_code(psi0)
+        _bind_torch_stream(model, psi0)
+        phi = torch.empty(0 if dst is None else dst.N, dtype=torch.complex128, device=psi0.device)
+        if dst is not None:
+            check(lib().sd_spm_q_dev(ctx.h, model.h, dst.h, op, code, psi0.data_ptr(), len(psi0), float(q), phi.data_ptr(),
+                                     dst.N), ctx.h)
+        return phi
+    psi0 = np.ascontiguousarray(psi0)
+    if psi0.dtype not in (np.float64, np.complex128):
+        psi0 = psi0.astype(np.complex128 if np.iscomplexobj(psi0) else np.float64)
+    phi = np.zeros(0 if dst is None else dst.N, dtype=np.complex128)
+    if dst is not None:
+        check(lib().sd_spm_q(ctx.h, model.h, dst.h, op, _dtype_code(psi0), psi0.ctypes.data, len(psi0), float(q),
+                             phi.ctypes.data, dst.N), ctx.h)
+    return phi
+
+
+def Sminus_q_vector(model, psi0, q):
+    """S^-_q psi0 with S^-_q = L^(-1/2) sum_r e^{iqr} S^-_{r+1} (the convention of Sz_q_vector).  psi0 lives in `model`'s
+    sector nup; the result is a new ComplexF64 vector of sector nup - 1 (model.adjacent_sector(-1)), of the full basis for a
+    full-basis model, and empty for nup = 0.  numpy in, numpy out; a torch CUDA tensor gives a tensor on the same stream."""
+    return _spm_q_vector(model, psi0, q, 2)
+
+
+def Splus_q_vector(model, psi0, q):
+    """S^+_q psi0, the same as Sminus_q_vector with S^+: the result lives in sector nup + 1 (empty for nup = L)."""
+    return _spm_q_vector(model, psi0, q, 1)
+
+
 _SPIN_OPS = {"z": 0, "plus": 1, "minus": 2, "x": 3, "y": 4}
 
 

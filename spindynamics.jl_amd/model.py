@@ -116,6 +116,23 @@ class Model:
 
         ctx.install_apply(_lib.APPLY_FN(tramp), me)
 
+    def adjacent_sector(self, dnup):
+        """The model with the same lists and context on sector nup + dnup (dnup = +1 or -1): the intermediate states of the
+        transverse structure factor (S^-_q maps sector nup to nup - 1, S^+_q to nup + 1).  Built once and kept with this
+        model, so a large plan is built once per pair of sectors.  ArgumentError for the full basis or a target outside 0..L."""
+        if dnup not in (1, -1):
+            raise ArgumentError("dnup must be +1 or -1")
+        if self.nup is None:
+            raise ArgumentError("the full basis has no adjacent sector: S^+- act inside it")
+        t = self.nup + int(dnup)
+        if t < 0 or t > self.L:
+            raise ArgumentError(f"sector nup = {t} is outside 0..L = {self.L}")
+        cache = self.__dict__.setdefault("_adjacent", {})
+        if t not in cache:
+            cache[t] = Model(self.L, nup=t, hopping=self.hopping_list, onsite_field=self.onsite_field, zz=self.zz_list,
+                             ctx=self.ctx)
+        return cache[t]
+
     # -- basis queries (host) --
     def states_range(self, start, count):
         out = np.empty(count, dtype=np.uint64)

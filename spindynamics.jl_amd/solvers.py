@@ -259,6 +259,59 @@ def lanczos_sqw(psi0, model, q_list, omega, lanc_m=200, eta=0.05, broaden="loren
     return S
 
 
+_COMPONENTS = {"+-": (2,), "-+": (1,), "xx": (2, 1)}
+
+
+def _transverse(psi0, model, q_list, omega, component, run):
+    """S^{+-} (op 2: S^-_q, sector nup - 1), S^{-+} (op 1: S^+_q, sector nup + 1) or S^{xx} = (S^{+-} + S^{-+}) / 4.  A
+    component without a target sector (S^{+-} at nup = 0, S^{-+} at nup = L) has phi = 0: its rows are zero."""
+    from .hamiltonian import _transverse_target
+    if component not in _COMPONENTS:
+        raise ArgumentError(f"unknown component: {component}; expected \"+-\", \"-+\" or \"xx\"")
+    x, code = _vec(psi0)
+    if len(x) != model.N:
+        raise DimensionMismatch(f"psi0 has length {len(x)}, expected {model.N}")
+    q = np.ascontiguousarray(q_list, dtype=np.float64)
+    om = np.ascontiguousarray(omega, dtype=np.float64)
+    parts = []
+    for op in _COMPONENTS[component]:
+        S = np.zeros((len(q), len(om)))
+        dst = _transverse_target(model, op)
+        if dst is not None:
+            run(dst, op, x, code, q, om, S)
+        parts.append(S)
+    if component == "xx":
+        return 0.25 * (parts[0] + parts[1])
+    return parts[0]
+
+
+def kpm_sqw_transverse(psi0, model, q_list, omega, component="+-", a=None, b=None, kpm_m=200, kernel="jackson", seed=0):
+    """kpm_sqw with phi = S^-_q psi0 ("+-"), S^+_q psi0 ("-+"), or S^{xx} = S^{yy} = (S^{+-} + S^{-+}) / 4 ("xx") -> Smat[Qn, W].
+    E0 = <psi0|H psi0> on psi0's sector; bounds (estimated per target sector when a, b are not given), moments and
+    reconstruction on the target sector's H (model.adjacent_sector)."""
+    have = a is not None and b is not None
+
+    def run(dst, op, x, code, q, om, S):
+        check(lib().sd_kpm_sqw_transverse(model.ctx.h, model.h, dst.h, op, code, x.ctypes.data, len(x), q.ctypes.data_as(_dp),
+                                          len(q), om.ctypes.data_as(_dp), len(om), int(have), float(a) if have else 0.0,
+                                          float(b) if have else 0.0, int(kpm_m), _lib.KERNELS.get(kernel, 2), int(seed),
+                                          S.ctypes.data_as(_dp)), model.ctx.h)
+    return _transverse(psi0, model, q_list, omega, component, run)
+
+
+def lanczos_sqw_transverse(psi0, model, q_list, omega, component="+-", lanc_m=200, eta=0.05, broaden="lorentz"):
+    """lanczos_sqw with phi = S^-_q psi0 ("+-"), S^+_q psi0 ("-+"), or their mean over the two ("xx", S^{xx} = S^{yy})
+    -> Smat[Qn, W].  E0 as lanczos_sqw forms it, on psi0's sector; the tridiagonal on the target sector's H."""
+    if broaden not in _lib.BROADEN:
+        raise ArgumentError(f"unknown broadening: {broaden}")
+
+    def run(dst, op, x, code, q, om, S):
+        check(lib().sd_lanczos_sqw_transverse(model.ctx.h, model.h, dst.h, op, code, x.ctypes.data, len(x),
+                                              q.ctypes.data_as(_dp), len(q), om.ctypes.data_as(_dp), len(om), int(lanc_m),
+                                              float(eta), _lib.BROADEN[broaden], S.ctypes.data_as(_dp)), model.ctx.h)
+    return _transverse(psi0, model, q_list, omega, component, run)
+
+
 def symtridiag_eig(d, e, vectors=True):
     d = np.ascontiguousarray(d, dtype=np.float64)
     e = np.ascontiguousarray(e, dtype=np.float64)
