@@ -26,17 +26,19 @@ namespace {
 
 #define RC(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 // No C++ exception may cross the C ABI: a failed host allocation (std::vector of the m x m work, std::string of a message) inside a
-// recursion comes back as a status.
-#define SD_ABI_GUARD(ctx, call)                                                                              \
-  try {                                                                                                       \
-    return (call);                                                                                            \
-  } catch (const std::bad_alloc &) {                                                                          \
-    return (ctx) ? sd_set_err((ctx), SD_ENOMEM, "out of host memory inside the call") : SD_ENOMEM;           \
-  } catch (const std::exception &e__) {                                                                       \
-    return (ctx) ? sd_set_err((ctx), SD_EINTERNAL, std::string("unexpected exception: ") + e__.what()) : SD_EINTERNAL; \
-  } catch (...) {                                                                                             \
-    return (ctx) ? sd_set_err((ctx), SD_EINTERNAL, "unexpected exception") : SD_EINTERNAL;                   \
+// recursion comes back as a status.  Every extern "C" entry point below is abi_guard(ctx, [&]() -> int { body }).
+template <class F>
+int abi_guard(sd_ctx *ctx, F &&body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc &) {
+    return ctx ? sd_set_err(ctx, SD_ENOMEM, "out of host memory inside the call") : SD_ENOMEM;
+  } catch (const std::exception &e) {
+    return ctx ? sd_set_err(ctx, SD_EINTERNAL, std::string("unexpected exception: ") + e.what()) : SD_EINTERNAL;
+  } catch (...) {
+    return ctx ? sd_set_err(ctx, SD_EINTERNAL, "unexpected exception") : SD_EINTERNAL;
   }
+}
 
 struct DBuf {   // device work vector, taken from / returned to the context's pool
   double *p = nullptr;
@@ -70,7 +72,7 @@ int d2d(sd_ctx *ctx, double *dst, const double *src, int64_t doubles) {
 
 // The caller's operator (sd_ctx_set_apply_callback; the reference's `applyH!` argument): out <- H psi by the callback on the
 // context's stream, then the recursion's fused step as one elementwise pass over out.
-int user_op(sd_ctx *ctx, const sd_model *m, int dtype, double *out, const double *psi, int64_t n, int epi, const sd_epi_args &ea) {
+int user_op(sd_ctx *ctx, int dtype, double *out, const double *psi, int64_t n, int epi, const sd_epi_args &ea) {
   if (ctx->user_apply(ctx->user_apply_data, dtype, out, psi, n, (void *)ctx->stream))
     return sd_set_err(ctx, SD_ECOMM, "the apply callback returned an error");
   if (epi == SD_EPI_PLAIN && !ea.negate) return SD_OK;
@@ -80,7 +82,7 @@ int user_op(sd_ctx *ctx, const sd_model *m, int dtype, double *out, const double
 int plain_op(sd_ctx *ctx, const sd_model *m, int dtype, double *out, const double *psi) {
   sd_epi_args ea;
   ++ctx->n_applies;
-  if (ctx->user_apply) return user_op(ctx, m, dtype, out, psi, m->n_local, SD_EPI_PLAIN, ea);
+  if (ctx->user_apply) return user_op(ctx, dtype, out, psi, m->n_local, SD_EPI_PLAIN, ea);
   return sd_launch_apply(ctx, m, dtype, out, psi, SD_EPI_PLAIN, ea);
 }
 
@@ -114,7 +116,7 @@ struct Op {
   // out = epilogue(H psi) on the owned rows.  Sharded: pack (cell mode), post the exchange, interior tiles, wait, boundary tiles.
   int apply(int dtype, double *out, const double *psi, int epi, sd_epi_args ea) {
     ++ctx->n_applies;
-    if (use_callback && ctx->user_apply) return user_op(ctx, m, dtype, out, psi, n, epi, ea);
+    if (use_callback && ctx->user_apply) return user_op(ctx, dtype, out, psi, n, epi, ea);
     if (m->nranks == 1) return sd_launch_apply(ctx, m, dtype, out, psi, epi, ea, 0);
     ea.halo = halo.p;
     const void *src = psi;
@@ -214,69 +216,64 @@ int lanczos_fused(Op &op, int Qb, double *u0, int mm, int form, int negate, doub
   return SD_OK;
 }
 
-// lanczos_extremal on device vectors; v_prev (2n doubles, un-normalised start) is consumed
-int extremal_dev(Op &op, int lanc_m, double tol, double *v_prev, int negate, double *emin, double *emax) {
+// The un-reorthogonalised Lanczos coefficients of one NORMALISED start vector u0 (2n doubles, consumed), two live vectors:
+// form 0 is lanczos_extremal's recursion (src/Lanczos.jl:27-84), form 1 lanczos_tridiag's (:196-246).  al, be: mm entries
+// (be[mm-1] unused).  The caller applies the reference's break on beta_j < tol to them: the steps before it are unaffected by
+// what was queued behind them, the rest is discarded.  last_always: the step of alpha_mm is queued even behind a breakdown seen
+// on the way (:237-239 stands after lanczos_tridiag's loop), so the betas are not looked at once it is the only step left.
+int lanczos_coeffs(Op &op, double *u0, int mm, int form, int negate, double tol, bool last_always, std::vector<double> &al,
+                   std::vector<double> &be) {
+  if (lanczos_fused_ok(op, 1)) return lanczos_fused(op, 1, u0, mm, form, negate, tol, al, be);   // launch-bound sizes: two launches per step
+  // No host round trip inside the loop: alpha_j, beta_j stay on the device (the update pass reads them there and files them
+  // into d_al / d_be): the recursion is queued at once and read back once.  The vectors stay un-normalised (u_{j+1} = w_j,
+  // |w_j|^2 on the device): the update divides on the fly and the normalising pass of :227/:233 disappears (k_lanczos_fold).
   sd_ctx *ctx = op.ctx;
   const int64_t N = op.n;
-  const int mm = (int)std::min<int64_t>(lanc_m, op.m->N);
-  if (mm < 1) return sd_set_err(ctx, SD_EARG, "lanc_m must be >= 1");
-  int rc = 0;
-  double nrm = norm_dev(op, v_prev, 2 * N, &rc); RC(rc);
-  RC(sd_k_scale_div(ctx, v_prev, v_prev, 2 * N, nrm));                     // :40
-  if (lanczos_fused_ok(op, 1)) {                                           // launch-bound sizes: two launches per step
-    std::vector<double> al, be;
-    RC(lanczos_fused(op, 1, v_prev, mm, 0, negate, tol, al, be));
-    int actual = mm;
-    for (int j = 1; j < mm; ++j)
-      if (!(be[j - 1] >= tol)) { actual = j; break; }                      // :66-70
-    std::vector<double> ev(actual);
-    if (sd_symtridiag_eig(actual, al.data(), be.data(), ev.data(), nullptr))   // :80-83
-      return sd_set_err(ctx, SD_EINTERNAL, "tridiagonal eigen-solver did not converge");
-    *emin = ev[0]; *emax = ev[actual - 1];
-    return SD_OK;
-  }
-  // the loop is queued without host round trips (alpha_j, beta_j stay on the device, see tridiag_dev); the break on
-  // beta_j < tol (:66-70) is applied to the values read back at the end.  Vectors stay un-normalised (k_lanczos_fold).
   DBuf w, vc, ab;
   RC(w.alloc(ctx, 2 * N)); RC(vc.alloc(ctx, 2 * N)); RC(ab.alloc(ctx, 4 * (int64_t)mm + 2));
   double *d_al = ab.p, *d_be = ab.p + mm, *d_n2 = ab.p + 2 * (int64_t)mm;      // d_n2[2j]: |w_j|^2
   SD_HIP(ctx, hipMemsetAsync(ab.p, 0, sizeof(double) * (4 * (size_t)mm + 2), ctx->stream));
   sd_epi_args ea; ea.negate = negate;
   std::vector<double> peek;
-  double *ucur = v_prev, *uprev = vc.p, *t = w.p;
+  double *ucur = u0, *uprev = vc.p, *t = w.p;
   const double *n2c = nullptr, *n2p = nullptr;       // |ucur|^2, |uprev|^2 on the device; null: normalised
   for (int j = 1; j <= mm; ++j) {
-    RC(op.apply(SD_C128, t, ucur, SD_EPI_DOT, ea));                        // :51 + :55 fused -> d_scalars[0]
+    RC(op.apply(SD_C128, t, ucur, SD_EPI_DOT, ea));                        // :51 + :55 / :218-219 fused -> d_scalars[0]
     RC(op.reduce(ctx->d_scalars + 0, 2));
-    if (j == mm) {                                                         // alpha_m; no vector behind it
-      RC(sd_k_lanczos_fold_scalars(ctx, 0, ctx->d_scalars + 0, n2c, d_al + (j - 1), j > 1 ? d_be + (j - 2) : nullptr));
+    if (j == mm) {                                                         // alpha_m; no vector behind it (:237-239)
+      RC(sd_k_lanczos_fold_scalars(ctx, form, ctx->d_scalars + 0, n2c, d_al + (j - 1), j > 1 ? d_be + (j - 2) : nullptr));
       break;
     }
     double *n2o = d_n2 + 2 * (int64_t)j;
-    RC(sd_k_lanczos_fold(ctx, t, ucur, j == 1 ? nullptr : uprev, N, 0, ctx->d_scalars + 0, n2c, n2p, d_al + (j - 1),
-                         j > 1 ? d_be + (j - 2) : nullptr, n2o));          // :58-65 (beta_{j-1} is filed by this pass)
+    RC(sd_k_lanczos_fold(ctx, t, ucur, j > 1 ? uprev : nullptr, N, form, ctx->d_scalars + 0, n2c, n2p, d_al + (j - 1),
+                         j > 1 ? d_be + (j - 2) : nullptr, n2o));          // :58-65 / :222-227 (beta_{j-1} is filed by this pass)
     RC(op.reduce(n2o, 1));
     { double *old = uprev; uprev = ucur; ucur = t; t = old; }
     n2p = n2c; n2c = n2o;
-    if (j % SD_BREAK_PEEK == 0 && j < mm) {
+    if (j % SD_BREAK_PEEK == 0 && j < (last_always ? mm - 1 : mm)) {       // bound the work queued behind a breakdown: look at the betas so far
       bool broke = false;
       RC(peek_breakdown(ctx, d_be, j - 1, tol, peek, &broke));
-      if (broke) break;
+      if (broke && !last_always) break;
+      if (broke) j = mm - 1;                                               // on to the step of alpha_mm
     }
   }
   std::vector<double> host(2 * (size_t)mm);
   SD_HIP(ctx, hipMemcpyAsync(host.data(), ab.p, sizeof(double) * 2 * (size_t)mm, hipMemcpyDeviceToHost, ctx->stream));
   SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  al.assign(host.begin(), host.begin() + mm); be.assign(host.begin() + mm, host.end());
+  return SD_OK;
+}
+
+// the reference's break on beta_j < tol (src/Lanczos.jl:66-70) applied to the read-back coefficients, then the extremal
+// eigenvalues of the tridiagonal matrix that is left (:80-83)
+int extremal_from_coeffs(sd_ctx *ctx, int mm, double tol, const double *al, const double *be, double *lo, double *hi) {
   int actual = mm;
   for (int j = 1; j < mm; ++j)
-    if (!(host[mm + j - 1] >= tol)) { actual = j; break; }                 // :66-70
-  std::vector<double> alpha(host.begin(), host.begin() + mm), beta(host.begin() + mm, host.end());
+    if (!(be[j - 1] >= tol)) { actual = j; break; }                        // :66-70
   std::vector<double> ev(actual);
-  int rce = sd_symtridiag_eig(actual, alpha.data(), beta.data(), ev.data(), nullptr);   // :80-83
-  if (rce) return sd_set_err(ctx, SD_EINTERNAL, "tridiagonal eigen-solver did not converge");
-  *emin = ev[0]; *emax = ev[actual - 1];
-  // note: v_prev / v_curr may have been swapped; the caller's buffer is scratch from here on
-  (void)hipStreamSynchronize(ctx->stream);
+  if (sd_symtridiag_eig(actual, al, be, ev.data(), nullptr))               // :80-83
+    return sd_set_err(ctx, SD_EINTERNAL, "tridiagonal eigen-solver did not converge");
+  *lo = ev[0]; *hi = ev[actual - 1];
   return SD_OK;
 }
 
@@ -286,6 +283,22 @@ int start_vector_op(Op &op, double *d, const void *given, bool given_on_dev, int
   if (given) return given_on_dev ? d2d(op.ctx, d, (const double *)given, doubles) : h2d(op.ctx, d, given, doubles);
   if (op.m->nranks > 1) return sd_launch_fill_randn_local(op.ctx, op.m, SD_C128, d, seed);
   return sd_k_fill_randn(op.ctx, d, doubles, seed, 0);
+}
+
+// lanczos_extremal from the caller's start vector (host or device pointer) or, without one, the seeded random vector
+int extremal_dev(Op &op, int lanc_m, double tol, const void *given, bool given_on_dev, uint64_t seed, int negate, double *emin,
+                 double *emax) {
+  sd_ctx *ctx = op.ctx;
+  const int mm = (int)std::min<int64_t>(lanc_m, op.m->N);
+  if (mm < 1) return sd_set_err(ctx, SD_EARG, "lanc_m must be >= 1");
+  DBuf v; RC(v.alloc(ctx, 2 * op.n));
+  RC(start_vector_op(op, v.p, given, given_on_dev, 2 * op.n, seed));
+  int rc = 0;
+  double nrm = norm_dev(op, v.p, 2 * op.n, &rc); RC(rc);
+  RC(sd_k_scale_div(ctx, v.p, v.p, 2 * op.n, nrm));                        // :40
+  std::vector<double> al, be;
+  RC(lanczos_coeffs(op, v.p, mm, 0, negate, tol, false, al, be));
+  return extremal_from_coeffs(ctx, mm, tol, al.data(), be.data(), emin, emax);
 }
 
 int moments_dev(Op &op, const double *phi, int M, double a, double b, double *mu) {
@@ -419,54 +432,12 @@ void tridiag_trim(int mm, double tol, const double *al, const double *be, double
   *m_eff_out = m_eff;
 }
 
-int tridiag_dev(Op &op, double *vcur /* normalised start, consumed */, int lanc_m, double tol,
-                double *alpha, double *beta, int *m_eff_out) {
-  // lanczos_tridiag  src/Lanczos.jl:196-246 with two live vectors (the reference keeps all m).
-  // No host round trip inside the loop: alpha_j and beta_j stay on the device (the update and normalisation passes read
-  // them there and file them into d_al / d_be), so the whole recursion is queued at once and read back once.  The
-  // reference's break on beta_j < tol (:228-231) is applied afterwards: the steps before it are unaffected by what was
-  // queued behind them, the rest is discarded.
-  sd_ctx *ctx = op.ctx;
-  const int64_t n = op.n;
+// lanczos_tridiag (src/Lanczos.jl:196-246) on a normalised device vector (consumed)
+int tridiag_dev(Op &op, double *vcur, int lanc_m, double tol, double *alpha, double *beta, int *m_eff_out) {
   const int mm = (int)std::min<int64_t>(lanc_m, op.m->N);
-  if (lanczos_fused_ok(op, 1)) {                                           // launch-bound sizes: two launches per step
-    std::vector<double> al, be;
-    RC(lanczos_fused(op, 1, vcur, mm, 1, 0, tol, al, be));
-    tridiag_trim(mm, tol, al.data(), be.data(), alpha, beta, m_eff_out);
-    return SD_OK;
-  }
-  DBuf wb, vp, ab;
-  RC(wb.alloc(ctx, 2 * n)); RC(vp.alloc(ctx, 2 * n)); RC(ab.alloc(ctx, 4 * (int64_t)mm + 2));
-  double *d_al = ab.p, *d_be = ab.p + mm, *d_n2 = ab.p + 2 * (int64_t)mm;      // d_n2[2j]: |w_j|^2
-  SD_HIP(ctx, hipMemsetAsync(ab.p, 0, sizeof(double) * (4 * (size_t)mm + 2), ctx->stream));
-  sd_epi_args ea;
-  std::vector<double> peek;
-  // the vectors stay un-normalised (u_{j+1} = w_j, |w_j|^2 on the device): the update pass divides on the fly and the
-  // normalising pass of :227/:233 disappears (k_lanczos_fold)
-  double *ucur = vcur, *uprev = vp.p, *t = wb.p;
-  const double *n2c = nullptr, *n2p = nullptr;
-  for (int j = 1; j <= mm - 1; ++j) {
-    RC(op.apply(SD_C128, t, ucur, SD_EPI_DOT, ea));                                                // :218-219 -> d_scalars[0]
-    RC(op.reduce(ctx->d_scalars + 0, 2));
-    double *n2o = d_n2 + 2 * (int64_t)j;
-    RC(sd_k_lanczos_fold(ctx, t, ucur, j > 1 ? uprev : nullptr, n, 1, ctx->d_scalars + 0, n2c, n2p, d_al + (j - 1),
-                         j > 1 ? d_be + (j - 2) : nullptr, n2o));                                  // :222-227
-    RC(op.reduce(n2o, 1));
-    { double *old = uprev; uprev = ucur; ucur = t; t = old; }
-    n2p = n2c; n2c = n2o;
-    if (j % SD_BREAK_PEEK == 0 && j < mm - 1) {       // bound the work queued behind a breakdown: look at the betas so far
-      bool broke = false;
-      RC(peek_breakdown(ctx, d_be, j - 1, tol, peek, &broke));
-      if (broke) break;
-    }
-  }
-  RC(op.apply(SD_C128, t, ucur, SD_EPI_DOT, ea));                                                  // :237-239
-  RC(op.reduce(ctx->d_scalars + 0, 2));
-  RC(sd_k_lanczos_fold_scalars(ctx, 1, ctx->d_scalars + 0, n2c, d_al + (mm - 1), mm > 1 ? d_be + (mm - 2) : nullptr));
-  std::vector<double> host(2 * (size_t)mm);
-  SD_HIP(ctx, hipMemcpyAsync(host.data(), ab.p, sizeof(double) * 2 * (size_t)mm, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  tridiag_trim(mm, tol, host.data(), host.data() + mm, alpha, beta, m_eff_out);
+  std::vector<double> al, be;
+  RC(lanczos_coeffs(op, vcur, mm, 1, 0, tol, true, al, be));
+  tridiag_trim(mm, tol, al.data(), be.data(), alpha, beta, m_eff_out);
   return SD_OK;
 }
 
@@ -645,82 +616,49 @@ static int energy_bounds_core(Op &op, int lanc_m, const void *psi0_a, const void
     }
     std::vector<double> al, be;
     RC(lanczos_fused(op, 2, v.p, mm, 0, /*negate mask: vector 1*/ 2, 1e-12, al, be));
-    for (int k = 0; k < 2; ++k) {
-      const double *a = al.data() + (size_t)k * mm, *b = be.data() + (size_t)k * mm;
-      int actual = mm;
-      for (int j = 1; j < mm; ++j)
-        if (!(b[j - 1] >= 1e-12)) { actual = j; break; }                                 // :66-70
-      std::vector<double> ev(actual);
-      if (sd_symtridiag_eig(actual, a, b, ev.data(), nullptr)) return sd_set_err(ctx, SD_EINTERNAL, "tridiagonal eigen-solver did not converge");
-      if (k == 0) *Emax = ev[actual - 1]; else *Emin = -ev[actual - 1];
-    }
+    RC(extremal_from_coeffs(ctx, mm, 1e-12, al.data(), be.data(), &lo, &hi));
+    *Emax = hi;
+    RC(extremal_from_coeffs(ctx, mm, 1e-12, al.data() + mm, be.data() + mm, &lo, &hi));
+    *Emin = -hi;
     return SD_OK;
   }
-  {
-    DBuf v; RC(v.alloc(ctx, 2 * op.n));
-    RC(start_vector_op(op, v.p, psi0_a, on_dev, 2 * op.n, seed));
-    RC(extremal_dev(op, lanc_m, 1e-12, v.p, 0, &lo, &hi));              // src/Lanczos.jl:258
-    *Emax = hi;
-  }
-  {
-    DBuf v; RC(v.alloc(ctx, 2 * op.n));
-    RC(start_vector_op(op, v.p, psi0_b, on_dev, 2 * op.n, seed + 0x9E3779B97F4A7C15ULL));
-    RC(extremal_dev(op, lanc_m, 1e-12, v.p, 1, &lo, &hi));              // :261-267
-    *Emin = -hi;
-  }
+  RC(extremal_dev(op, lanc_m, 1e-12, psi0_a, on_dev, seed, 0, &lo, &hi));                            // src/Lanczos.jl:258
+  *Emax = hi;
+  RC(extremal_dev(op, lanc_m, 1e-12, psi0_b, on_dev, seed + 0x9E3779B97F4A7C15ULL, 1, &lo, &hi));   // :261-267
+  *Emin = -hi;
   return SD_OK;
 }
 
-static int sd_lanczos_extremal_impl(sd_ctx *ctx, const sd_model *m, int lanc_m, double tol, const void *psi0,
-                                   uint64_t seed, int negate, double *emin, double *emax) {
+extern "C" int sd_lanczos_extremal(sd_ctx *ctx, const sd_model *m, int lanc_m, double tol, const void *psi0,
+                                   uint64_t seed, int negate, double *emin, double *emax) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, nullptr));
   if (!emin || !emax) return sd_set_err(ctx, SD_EARG, "null output");
-  DBuf v; RC(v.alloc(ctx, 2 * op.n));
-  RC(start_vector_op(op, v.p, psi0, false, 2 * op.n, seed));
-  return extremal_dev(op, lanc_m, tol, v.p, negate, emin, emax);
-}
-extern "C" int sd_lanczos_extremal(sd_ctx *ctx, const sd_model *m, int lanc_m, double tol, const void *psi0,
-                                   uint64_t seed, int negate, double *emin, double *emax) {
-  SD_ABI_GUARD(ctx, sd_lanczos_extremal_impl(ctx, m, lanc_m, tol, psi0, seed, negate, emin, emax));
-}
+  return extremal_dev(op, lanc_m, tol, psi0, false, seed, negate, emin, emax);
+}); }
 
-static int sd_lanczos_extremal_sharded_impl(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int lanc_m, double tol,
-                                           const void *psi0_dev, uint64_t seed, int negate, double *emin, double *emax) {
+extern "C" int sd_lanczos_extremal_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int lanc_m, double tol, const void *psi0_dev,
+                                           uint64_t seed, int negate, double *emin, double *emax) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, comm));
   if (!emin || !emax) return sd_set_err(ctx, SD_EARG, "null output");
-  DBuf v; RC(v.alloc(ctx, 2 * op.n));
-  RC(start_vector_op(op, v.p, psi0_dev, true, 2 * op.n, seed));
-  return extremal_dev(op, lanc_m, tol, v.p, negate, emin, emax);
-}
-extern "C" int sd_lanczos_extremal_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int lanc_m, double tol,
-                                           const void *psi0_dev, uint64_t seed, int negate, double *emin, double *emax) {
-  SD_ABI_GUARD(ctx, sd_lanczos_extremal_sharded_impl(ctx, m, comm, lanc_m, tol, psi0_dev, seed, negate, emin, emax));
-}
+  return extremal_dev(op, lanc_m, tol, psi0_dev, true, seed, negate, emin, emax);
+}); }
 
-static int sd_energy_bounds_impl(sd_ctx *ctx, const sd_model *m, int lanc_m, const void *psi0_a, const void *psi0_b,
-                                uint64_t seed, double *Emin, double *Emax) {
+extern "C" int sd_energy_bounds(sd_ctx *ctx, const sd_model *m, int lanc_m, const void *psi0_a, const void *psi0_b,
+                                uint64_t seed, double *Emin, double *Emax) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, nullptr));
   if (!Emin || !Emax) return sd_set_err(ctx, SD_EARG, "null output");
   return energy_bounds_core(op, lanc_m, psi0_a, psi0_b, false, seed, Emin, Emax);
-}
-extern "C" int sd_energy_bounds(sd_ctx *ctx, const sd_model *m, int lanc_m, const void *psi0_a, const void *psi0_b,
-                                uint64_t seed, double *Emin, double *Emax) {
-  SD_ABI_GUARD(ctx, sd_energy_bounds_impl(ctx, m, lanc_m, psi0_a, psi0_b, seed, Emin, Emax));
-}
+}); }
 
-static int sd_energy_bounds_sharded_impl(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int lanc_m, uint64_t seed,
-                                        double *Emin, double *Emax) {
+extern "C" int sd_energy_bounds_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int lanc_m, uint64_t seed,
+                                        double *Emin, double *Emax) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, comm));
   if (!Emin || !Emax) return sd_set_err(ctx, SD_EARG, "null output");
   return energy_bounds_core(op, lanc_m, nullptr, nullptr, true, seed, Emin, Emax);
-}
-extern "C" int sd_energy_bounds_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int lanc_m, uint64_t seed,
-                                        double *Emin, double *Emax) {
-  SD_ABI_GUARD(ctx, sd_energy_bounds_sharded_impl(ctx, m, comm, lanc_m, seed, Emin, Emax));
-}
+}); }
 
-static int sd_apply_sharded_impl(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int dtype, void *out_dev, const void *psi_dev,
-                                int64_t n_local, int overlap) {
+extern "C" int sd_apply_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int dtype, void *out_dev, const void *psi_dev,
+                                int64_t n_local, int overlap) { return abi_guard(ctx, [&]() -> int {
   if (!ctx) return SD_EARG;
   if (!m || !out_dev || !psi_dev) return sd_set_err(ctx, SD_EARG, "null argument");
   if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
@@ -733,14 +671,10 @@ static int sd_apply_sharded_impl(sd_ctx *ctx, const sd_model *m, sd_comm *comm, 
   RC(op.apply(dtype, (double *)out_dev, (const double *)psi_dev, SD_EPI_PLAIN, ea));
   SD_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the halo / send buffers go back to the pool
   return SD_OK;
-}
-extern "C" int sd_apply_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int dtype, void *out_dev, const void *psi_dev,
-                                int64_t n_local, int overlap) {
-  SD_ABI_GUARD(ctx, sd_apply_sharded_impl(ctx, m, comm, dtype, out_dev, psi_dev, n_local, overlap));
-}
+}); }
 
-static int sd_dot_sharded_impl(sd_ctx *ctx, sd_comm *comm, int dtype, const void *x, const void *y, int64_t n_local,
-                              double *out2) {
+extern "C" int sd_dot_sharded(sd_ctx *ctx, sd_comm *comm, int dtype, const void *x, const void *y, int64_t n_local,
+                              double *out2) { return abi_guard(ctx, [&]() -> int {
   if (!ctx) return SD_EARG;
   if (!x || !y || !out2 || n_local < 0) return sd_set_err(ctx, SD_EARG, "bad argument");
   if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
@@ -748,14 +682,10 @@ static int sd_dot_sharded_impl(sd_ctx *ctx, sd_comm *comm, int dtype, const void
   RC(sd_k_dot(ctx, dtype == SD_C128 ? 2 : 1, (const double *)x, (const double *)y, n_local, 4));
   RC(sd_comm_allreduce_dev(ctx, comm, ctx->d_scalars + 4, 2));
   return sd_read_scalars(ctx, 4, 2, out2);
-}
-extern "C" int sd_dot_sharded(sd_ctx *ctx, sd_comm *comm, int dtype, const void *x, const void *y, int64_t n_local,
-                              double *out2) {
-  SD_ABI_GUARD(ctx, sd_dot_sharded_impl(ctx, comm, dtype, x, y, n_local, out2));
-}
+}); }
 
-static int sd_lanczos_groundstate_impl(sd_ctx *ctx, const sd_model *m, int lanc_m, double tol, double orth_tol,
-                                      const double *psi0, uint64_t seed, double *E0, double *psi_gs, int *m_actual_out) {
+extern "C" int sd_lanczos_groundstate(sd_ctx *ctx, const sd_model *m, int lanc_m, double tol, double orth_tol, const double *psi0,
+                                      uint64_t seed, double *E0, double *psi_gs, int *m_actual_out) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, nullptr));
   if (!E0 || !psi_gs) return sd_set_err(ctx, SD_EARG, "null output");
   const int64_t N = m->N;
@@ -771,7 +701,9 @@ static int sd_lanczos_groundstate_impl(sd_ctx *ctx, const sd_model *m, int lanc_
   std::vector<double> alpha(mm, 0.0), beta(mm, 0.0);
   int m_actual = mm;
   // The reference's orthogonality check of step j (:142-153: dot(V[:,k], w/beta) for every k <= j) as the sequential loop
-  // would run it, from column k0 on: corrects w and beta[j-1] when a test fires.  Returns 1 on breakdown (beta < tol).
+  // would run it: corrects w and beta[j-1] when a test fires; *broke = 1 on breakdown (beta < tol).  The tests between two
+  // corrections all use the same w/beta, so they are taken in one pass (sd_k_mdot) and the first one that fires is handled
+  // exactly as the reference's sequential loop would; the rest is tested again.
   auto check_and_correct = [&](int j, double *wj, double *scratch_vec, int *broke) -> int {
     double s[2];
     std::vector<double> chk(j);
@@ -874,24 +806,9 @@ static int sd_lanczos_groundstate_impl(sd_ctx *ctx, const sd_model *m, int lanc_
     if (j < mm) {
       beta[j - 1] = norm_dev(op, w.p, N, &rc); RC(rc);                                   // :133
       if (beta[j - 1] < tol) { m_actual = j; break; }                                    // :136-139
-      // :142-153: for k = 1..j test |dot(V[:,k], w/beta)| > orth_tol and correct w when it fires (then w/beta changes).
-      // The tests between two corrections all use the same w/beta, so they are taken in one pass (sd_k_mdot) and the
-      // first one that fires is handled exactly as the reference's sequential loop would; the rest is tested again.
-      std::vector<double> chk(j);
-      for (int k = 1; k <= j;) {
-        RC(sd_k_scale_div(ctx, tmp.p, w.p, N, beta[j - 1]));
-        RC(sd_k_mdot(ctx, V.p + N * (int64_t)(k - 1), N, j - k + 1, tmp.p, N, chk.data()));
-        int hit = -1;
-        for (int q = 0; q < j - k + 1 && hit < 0; ++q)
-          if (std::fabs(chk[q]) > orth_tol) hit = k + q;
-        if (hit < 0) break;
-        double *vk = V.p + N * (int64_t)(hit - 1);
-        RC(sd_k_dot(ctx, 1, vk, w.p, N, 4)); RC(sd_read_scalars(ctx, 4, 1, s));
-        RC(sd_k_sub2(ctx, w.p, vk, nullptr, N, s[0], 0.0));
-        beta[j - 1] = norm_dev(op, w.p, N, &rc); RC(rc);
-        if (beta[j - 1] < tol) { m_actual = j; break; }                                 // inner break only (:150)
-        k = hit + 1;
-      }
+      int broke = 0;
+      RC(check_and_correct(j, w.p, tmp.p, &broke));                                      // :142-153
+      if (broke) m_actual = j;                                                           // inner break only (:150): the step goes on
       RC(sd_k_scale_div(ctx, V.p + N * (int64_t)j, w.p, N, beta[j - 1]));                 // :155
     }
   }
@@ -905,14 +822,10 @@ static int sd_lanczos_groundstate_impl(sd_ctx *ctx, const sd_model *m, int lanc_
   RC(d2h(ctx, psi_gs, w.p, N));
   if (m_actual_out) *m_actual_out = m_actual;
   return SD_OK;
-}
-extern "C" int sd_lanczos_groundstate(sd_ctx *ctx, const sd_model *m, int lanc_m, double tol, double orth_tol,
-                                      const double *psi0, uint64_t seed, double *E0, double *psi_gs, int *m_actual_out) {
-  SD_ABI_GUARD(ctx, sd_lanczos_groundstate_impl(ctx, m, lanc_m, tol, orth_tol, psi0, seed, E0, psi_gs, m_actual_out));
-}
+}); }
 
-static int sd_lanczos_tridiag_impl(sd_ctx *ctx, const sd_model *m, const void *v, int64_t n, int lanc_m, double tol,
-                                  double *alpha, double *beta, int *m_eff, double *norm_v) {
+extern "C" int sd_lanczos_tridiag(sd_ctx *ctx, const sd_model *m, const void *v, int64_t n, int lanc_m, double tol,
+                                  double *alpha, double *beta, int *m_eff, double *norm_v) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, nullptr));
   if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
   if (!v || !alpha || !beta || !m_eff || !norm_v) return sd_set_err(ctx, SD_EARG, "null argument");
@@ -925,11 +838,7 @@ static int sd_lanczos_tridiag_impl(sd_ctx *ctx, const sd_model *m, const void *v
   RC(sd_k_scale_div(ctx, vc.p, vc.p, 2 * n, normv));
   *norm_v = normv;
   return tridiag_dev(op, vc.p, lanc_m, tol, alpha, beta, m_eff);
-}
-extern "C" int sd_lanczos_tridiag(sd_ctx *ctx, const sd_model *m, const void *v, int64_t n, int lanc_m, double tol,
-                                  double *alpha, double *beta, int *m_eff, double *norm_v) {
-  SD_ABI_GUARD(ctx, sd_lanczos_tridiag_impl(ctx, m, v, n, lanc_m, tol, alpha, beta, m_eff, norm_v));
-}
+}); }
 
 // krylov_time_evolve; on_dev: psi0 / psit are device vectors (psit ComplexF64; may alias a ComplexF64 psi0)
 static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, double dt, int kry_m, void *psit, bool on_dev) {
@@ -957,7 +866,7 @@ static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, do
   RC(sd_k_promote(ctx, V[0].p, inp, nc, n));
   if (norm0 == 0) return emit(V[0].p);                                                    // :145-147
   RC(sd_k_scale_div(ctx, V[0].p, V[0].p, 2 * n, norm0));                                  // :148
-  // the Lanczos part is queued without host round trips (see tridiag_dev): alpha_j (complex) and beta_j stay on the device
+  // the Lanczos part is queued without host round trips (see lanczos_coeffs): alpha_j (complex) and beta_j stay on the device
   // and are read back once; the break on |beta_j| < 1e-14 (:162-168) is applied to the values afterwards
   // V[j] holds the un-normalised u_{j+1} = w_j (k_lanczos_fold): no normalising pass; the final combination divides its
   // coefficients by beta_j instead
@@ -1034,35 +943,23 @@ static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, do
   return emit(w.p);
 }
 
-static int sd_krylov_evolve_impl(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, double dt,
-                                int kry_m, void *psit) {
+extern "C" int sd_krylov_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, double dt,
+                                int kry_m, void *psit) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, nullptr));
   return krylov_evolve_core(op, dtype, psi0, n, dt, kry_m, psit, false);
-}
-extern "C" int sd_krylov_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, double dt,
-                                int kry_m, void *psit) {
-  SD_ABI_GUARD(ctx, sd_krylov_evolve_impl(ctx, m, dtype, psi0, n, dt, kry_m, psit));
-}
+}); }
 
-static int sd_krylov_evolve_dev_impl(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, double dt,
-                                    int kry_m, void *psit_dev) {
+extern "C" int sd_krylov_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, double dt,
+                                    int kry_m, void *psit_dev) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, nullptr));
   return krylov_evolve_core(op, dtype, psi0_dev, n, dt, kry_m, psit_dev, true);
-}
-extern "C" int sd_krylov_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, double dt,
-                                    int kry_m, void *psit_dev) {
-  SD_ABI_GUARD(ctx, sd_krylov_evolve_dev_impl(ctx, m, dtype, psi0_dev, n, dt, kry_m, psit_dev));
-}
+}); }
 
-static int sd_krylov_evolve_sharded_impl(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int dtype, const void *psi0_dev,
-                                        int64_t n_local, double dt, int kry_m, void *psit_dev) {
+extern "C" int sd_krylov_evolve_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int dtype, const void *psi0_dev,
+                                        int64_t n_local, double dt, int kry_m, void *psit_dev) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, comm));
   return krylov_evolve_core(op, dtype, psi0_dev, n_local, dt, kry_m, psit_dev, true);
-}
-extern "C" int sd_krylov_evolve_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int dtype, const void *psi0_dev,
-                                        int64_t n_local, double dt, int kry_m, void *psit_dev) {
-  SD_ABI_GUARD(ctx, sd_krylov_evolve_sharded_impl(ctx, m, comm, dtype, psi0_dev, n_local, dt, kry_m, psit_dev));
-}
+}); }
 
 // chebyshev_time_evolve on device vectors: psi0_dev (c128, n elements) is read, psit_dev receives psi(t); they may be the
 // same buffer (psi0 is copied into the recursion's own vectors first).  host_in / host_out select the host-pointer form.
@@ -1080,18 +977,17 @@ static int chebyshev_evolve_core(Op &op, const void *psi0, bool host_in, int64_t
   double *pprev = b0.p, *pcur = b1.p, *pnext = b2.p;
   if (host_in) RC(h2d(ctx, pprev, psi0, 2 * n));                                          // :90
   else RC(d2d(ctx, pprev, (const double *)psi0, 2 * n));
-  struct { double *p; } pt;                       // psi_t accumulates in the caller's device buffer when there is one
-  if (host_out) { RC(ptb.alloc(ctx, 2 * n)); pt.p = ptb.p; }
-  else pt.p = (double *)psit;
+  double *pt = (double *)psit;                    // psi_t accumulates in the caller's device buffer when there is one
+  if (host_out) { RC(ptb.alloc(ctx, 2 * n)); pt = ptb.p; }
   sd_epi_args ea; ea.a = a; ea.b = b;
   RC(op.apply(SD_C128, pcur, pprev, SD_EPI_RESCALE, ea));                                 // :93
-  RC(sd_k_cheb_init(ctx, pt.p, pprev, pcur, n, c[0], c[1], cheb_n >= 2 ? c[2] : 0.0, cheb_n >= 2 ? c[3] : 0.0,
+  RC(sd_k_cheb_init(ctx, pt, pprev, pcur, n, c[0], c[1], cheb_n >= 2 ? c[2] : 0.0, cheb_n >= 2 ? c[3] : 0.0,
                     cheb_n >= 2));                                                        // :96-102
   // :110-121, one fused pass per term.  Terms are taken in pairs: the first of a pair only advances the recurrence, the
   // second adds both terms to psi_t in order (c_k phi_k is exact in the apply's input vector), so psi_t is read and
   // written once per two terms -- same bits as one accumulation per term, 72 instead of 80 B/row per term.
   int k = 2;
-  ea.accv = pt.p;
+  ea.accv = pt;
   if ((cheb_n - 2) % 2 == 1) {
     ea.prev = pprev; ea.c_re = c[2 * k]; ea.c_im = c[2 * k + 1];
     RC(op.apply(SD_C128, pnext, pcur, SD_EPI_CHEB, ea));
@@ -1106,69 +1002,50 @@ static int chebyshev_evolve_core(Op &op, const void *psi0, bool host_in, int64_t
     RC(op.apply(SD_C128, pnext, pcur, SD_EPI_CHEB2, ea));                                 // phi_{k+1}; psi_t += c_k phi_k + c_{k+1} phi_{k+1}
     { double *t = pprev; pprev = pcur; pcur = pnext; pnext = t; }
   }
-  if (host_out) RC(d2h(ctx, psit, pt.p, 2 * n));
+  if (host_out) RC(d2h(ctx, psit, pt, 2 * n));
   else SD_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the work vectors go back to the pool: nothing may still use them
   return SD_OK;
 }
 
-static int sd_chebyshev_evolve_impl(sd_ctx *ctx, const sd_model *m, const void *psi0, int64_t n, double dt, int cheb_n,
-                                   double Emin, double Emax, void *psit) {
+extern "C" int sd_chebyshev_evolve(sd_ctx *ctx, const sd_model *m, const void *psi0, int64_t n, double dt, int cheb_n,
+                                   double Emin, double Emax, void *psit) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, nullptr));
   return chebyshev_evolve_core(op, psi0, true, n, dt, cheb_n, Emin, Emax, psit, true);
-}
-extern "C" int sd_chebyshev_evolve(sd_ctx *ctx, const sd_model *m, const void *psi0, int64_t n, double dt, int cheb_n,
-                                   double Emin, double Emax, void *psit) {
-  SD_ABI_GUARD(ctx, sd_chebyshev_evolve_impl(ctx, m, psi0, n, dt, cheb_n, Emin, Emax, psit));
-}
+}); }
 
-static int sd_chebyshev_evolve_dev_impl(sd_ctx *ctx, const sd_model *m, const void *psi0_dev, int64_t n, double dt, int cheb_n,
-                                       double Emin, double Emax, void *psit_dev) {
+extern "C" int sd_chebyshev_evolve_dev(sd_ctx *ctx, const sd_model *m, const void *psi0_dev, int64_t n, double dt, int cheb_n,
+                                       double Emin, double Emax, void *psit_dev) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, nullptr));
   return chebyshev_evolve_core(op, psi0_dev, false, n, dt, cheb_n, Emin, Emax, psit_dev, false);
-}
-extern "C" int sd_chebyshev_evolve_dev(sd_ctx *ctx, const sd_model *m, const void *psi0_dev, int64_t n, double dt, int cheb_n,
-                                       double Emin, double Emax, void *psit_dev) {
-  SD_ABI_GUARD(ctx, sd_chebyshev_evolve_dev_impl(ctx, m, psi0_dev, n, dt, cheb_n, Emin, Emax, psit_dev));
-}
+}); }
 
-static int sd_chebyshev_evolve_sharded_impl(sd_ctx *ctx, const sd_model *m, sd_comm *comm, const void *psi0_dev,
-                                           int64_t n_local, double dt, int cheb_n, double Emin, double Emax, void *psit_dev) {
+extern "C" int sd_chebyshev_evolve_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, const void *psi0_dev, int64_t n_local,
+                                           double dt, int cheb_n, double Emin, double Emax, void *psit_dev) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, comm));
   return chebyshev_evolve_core(op, psi0_dev, false, n_local, dt, cheb_n, Emin, Emax, psit_dev, false);
-}
-extern "C" int sd_chebyshev_evolve_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, const void *psi0_dev,
-                                           int64_t n_local, double dt, int cheb_n, double Emin, double Emax, void *psit_dev) {
-  SD_ABI_GUARD(ctx, sd_chebyshev_evolve_sharded_impl(ctx, m, comm, psi0_dev, n_local, dt, cheb_n, Emin, Emax, psit_dev));
-}
+}); }
 
-static int sd_kpm_moments_impl(sd_ctx *ctx, const sd_model *m, const void *phi, int64_t n, int M, double a, double b,
-                              double *mu) {
+extern "C" int sd_kpm_moments(sd_ctx *ctx, const sd_model *m, const void *phi, int64_t n, int M, double a, double b,
+                              double *mu) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, nullptr));
   if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
   if (!phi || !mu) return sd_set_err(ctx, SD_EARG, "null argument");
   DBuf ph; RC(ph.alloc(ctx, 2 * n));
   RC(h2d(ctx, ph.p, phi, 2 * n));
   return moments_dev(op, ph.p, M, a, b, mu);
-}
-extern "C" int sd_kpm_moments(sd_ctx *ctx, const sd_model *m, const void *phi, int64_t n, int M, double a, double b,
-                              double *mu) {
-  SD_ABI_GUARD(ctx, sd_kpm_moments_impl(ctx, m, phi, n, M, a, b, mu));
-}
+}); }
 
-static int sd_kpm_moments_sharded_impl(sd_ctx *ctx, const sd_model *m, sd_comm *comm, const void *phi_dev, int64_t n_local,
-                                      int M, double a, double b, double *mu) {
+extern "C" int sd_kpm_moments_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, const void *phi_dev, int64_t n_local,
+                                      int M, double a, double b, double *mu) { return abi_guard(ctx, [&]() -> int {
   Op op; RC(op.init(ctx, m, comm));
   if (n_local != op.n) return sd_set_err(ctx, SD_EDIM, "vector length does not match the local basis dimension");
   if (!phi_dev || !mu) return sd_set_err(ctx, SD_EARG, "null argument");
   RC(moments_dev(op, (const double *)phi_dev, M, a, b, mu));
   SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SD_OK;
-}
-extern "C" int sd_kpm_moments_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, const void *phi_dev, int64_t n_local,
-                                      int M, double a, double b, double *mu) {
-  SD_ABI_GUARD(ctx, sd_kpm_moments_sharded_impl(ctx, m, comm, phi_dev, n_local, M, a, b, mu));
-}
+}); }
 
+namespace {
 // H is real in the S^z basis, so for a real psi0 phi_{2pi-q} = conj(phi_q): the moments mu_n and the Lanczos coefficients
 // alpha_j, beta_j of q and of 2pi - q agree, and so do the rows S(q, w).  same_as[j] = i < j when q[j] = 2 pi k - q[i] (to 8 ulp)
 // and psi0 is real -- Float64, or ComplexF64 whose imaginary parts are all zero (counted on the device, summed over the ranks) --,
@@ -1198,224 +1075,201 @@ int pair_momenta(Op &op, int dtype, const double *psic, int64_t n, const double 
   return SD_OK;
 }
 
-// kpm_sqw (src/KPM_Sqw.jl:191-256); psi0: host vector (unsharded form) or this rank's rows on the device
-static int kpm_sqw_core(Op &op, int dtype, const void *psi0, bool on_dev, int64_t n, const double *q, int Qn,
-                        const double *omega, int W, int have_ab, double a, double b, int kpm_m, int kernel, uint64_t seed,
-                        double *Smat) {
-  sd_ctx *ctx = op.ctx;
-  const sd_model *m = op.m;
-  if (n != op.n) return sd_set_err(ctx, SD_EDIM, "vector length does not match the (local) basis dimension");
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
-  if (kpm_m < 2) return sd_set_err(ctx, SD_EARG, "kpm_m must be >= 2");
-  if (!psi0 || !Smat || (Qn > 0 && !q) || (W > 0 && !omega)) return sd_set_err(ctx, SD_EARG, "null argument");
-  const int nc = dtype == SD_C128 ? 2 : 1;
-  DBuf in, psic, phi;
-  RC(psic.alloc(ctx, 2 * n)); RC(phi.alloc(ctx, 2 * n));
-  const double *inp = (const double *)psi0;
-  if (!on_dev) { RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi0, nc * n)); inp = in.p; }
-  RC(sd_k_promote(ctx, psic.p, inp, nc, n));                                              // :202
-  in.release();
-  sd_epi_args ea;
-  double s[2];
-  // phi doubles as the scratch for H psi0 (only <psi0|H psi0> is kept): the recursion then holds psi0, phi and its three
-  // work vectors -- five vectors of n elements plus halo and send buffer on a shard
-  RC(op.apply(SD_C128, phi.p, psic.p, SD_EPI_DOT, ea));                                   // :208-209
-  RC(op.reduce(ctx->d_scalars + 0, 2));
-  RC(sd_read_scalars(ctx, 0, 2, s));
-  const double E0 = s[0];
-  if (!have_ab) {                                                                         // :212-214
-    double Emin, Emax;
-    RC(energy_bounds_core(op, 80, nullptr, nullptr, true, seed, &Emin, &Emax));
-    sd_kpm_rescaling_from_bounds(Emin, Emax, &a, &b);
-  }
-  std::vector<double> mu(kpm_m), g(kpm_m);
-  sd_kpm_kernel(kpm_m, kernel, g.data());
-  int rc = 0;
-  // every pair (q, 2 pi - q) of the list is computed once for a real psi0 (pair_momenta)
-  std::vector<int> same_as;
-  RC(pair_momenta(op, dtype, psic.p, n, q, Qn, same_as));
-  // Launch-bound sizes: the momenta's vectors share their launches (moments_dev_batched).  sd_ctx_set_q_batch(ctx, 0): one momentum at a time.
-  {
-    std::vector<int> live;
-    for (int iq = 0; iq < Qn; ++iq) if (same_as[iq] < 0) live.push_back(iq);
-    const int q_batch = ctx->q_batch;
-    const int Qb = (int)live.size();
-    // five batches of vectors (phi + the recursion's three + nothing else) within 4 GiB, vectors of at most 2^22 rows
-    const bool batched = q_batch && Qb >= 2 && m->nranks == 1 && !ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 16384 &&
-                         n <= ((int64_t)1 << 22) && (int64_t)Qb * n * 16 * 4 <= ((int64_t)4 << 30);
-    if (batched) {
-      DBuf phib, nrm;
-      RC(phib.alloc(ctx, 2 * n * Qb)); RC(nrm.alloc(ctx, 2 * (int64_t)Qb));
-      for (int k = 0; k < Qb; ++k) {
-        RC(sd_launch_szq(ctx, m, SD_C128, psic.p, q[live[k]], phib.p + 2 * n * k));       // :223
-        RC(sd_k_nrm2sq_to(ctx, phib.p + 2 * n * k, 2 * n, nrm.p + 2 * k));
-      }
-      std::vector<double> hn(2 * (size_t)Qb);
-      SD_HIP(ctx, hipMemcpyAsync(hn.data(), nrm.p, sizeof(double) * hn.size(), hipMemcpyDeviceToHost, ctx->stream));
-      SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      // zero vectors (:226-229) drop out of the batch; the rest are normalised in place (:231)
-      std::vector<int> kept; std::vector<double> norms;
-      for (int k = 0; k < Qb; ++k) {
-        const double nphi = std::sqrt(hn[2 * (size_t)k]);
-        double *Srow = Smat + (size_t)live[k] * W;
-        if (nphi == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }
-        const int dst = (int)kept.size();
-        if (dst != k) RC(d2d(ctx, phib.p + 2 * n * dst, phib.p + 2 * n * k, 2 * n));
-        RC(sd_k_scale_div(ctx, phib.p + 2 * n * dst, phib.p + 2 * n * dst, 2 * n, nphi));
-        kept.push_back(live[k]); norms.push_back(nphi);
-      }
-      const int Qk = (int)kept.size();
-      if (Qk > 0) {
-        std::vector<double> mub((size_t)Qk * (size_t)kpm_m);
-        std::vector<char> okv;
-        RC(moments_dev_batched(op, phib.p, Qk, kpm_m, a, b, mub.data(), okv));
-        for (int k = 0; k < Qk; ++k) {
-          double *Srow = Smat + (size_t)kept[k] * W;
-          double *muk = mub.data() + (size_t)k * (size_t)kpm_m;
-          if (!okv[k]) RC(moments_dev(op, phib.p + 2 * n * k, kpm_m, a, b, muk));          // the guard fired: the reference's loop
-          for (int j = 0; j < kpm_m; ++j) muk[j] *= g[j];                                 // :53
-          sd_kpm_reconstruct(muk, kpm_m, omega, W, a, b, E0, Srow);
-          const double n2 = norms[k] * norms[k];
-          for (int iw = 0; iw < W; ++iw) Srow[iw] *= n2;                                  // :252
-        }
-      }
-      for (int iq = 0; iq < Qn; ++iq)
-        if (same_as[iq] >= 0) std::memcpy(Smat + (size_t)iq * W, Smat + (size_t)same_as[iq] * W, sizeof(double) * (size_t)W);
-      SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      return SD_OK;
+// ---- S(q,w): kpm_sqw (src/KPM_Sqw.jl:191-256), lanczos_sqw (src/LanczosSqw.jl:47-80) and their transverse forms ----
+// How one row S(q, .) is made from phi_q -- all that differs between the KPM and the Lanczos calls.  The recursion runs on
+// `op`, the sector phi_q lives in; sqw_core below owns everything else.
+struct Spectrum {
+  Op &op;
+  const double *omega; int W;
+  double E0 = 0.0;
+  bool batchable = true;
+  Spectrum(Op &o, const double *om, int w) : op(o), omega(om), W(w) {}
+  virtual int check() const = 0;                                           // the method's own arguments
+  virtual int start(Op &os, const double *psic, double *scratch) = 0;      // E0 from psi0 (sector os; scratch: n elements), once per call
+  virtual bool can_batch(int Qb) const = 0;                                // may Qb momenta share their launches?
+  virtual int one(double *phi, double norm_phi, double *Srow) = 0;         // phi: normalised, consumed
+  virtual int batch(double *phib, int Qk, const double *norms, double *const *rows) = 0;   // Qk normalised vectors back to back
+};
+
+struct KpmSpectrum : Spectrum {
+  int have_ab; double a, b; int kpm_m, kernel; uint64_t seed;
+  std::vector<double> mu, g;
+  KpmSpectrum(Op &o, const double *om, int w, int have_ab_, double a_, double b_, int kpm_m_, int kernel_, uint64_t seed_)
+      : Spectrum(o, om, w), have_ab(have_ab_), a(a_), b(b_), kpm_m(kpm_m_), kernel(kernel_), seed(seed_) {}
+  int check() const override { return kpm_m < 2 ? sd_set_err(op.ctx, SD_EARG, "kpm_m must be >= 2") : SD_OK; }
+  int start(Op &os, const double *psic, double *scratch) override {
+    sd_ctx *ctx = os.ctx;
+    sd_epi_args ea;
+    double s[2];
+    RC(os.apply(SD_C128, scratch, psic, SD_EPI_DOT, ea));                                   // :208-209 (only <psi0|H psi0> is kept)
+    RC(os.reduce(ctx->d_scalars + 0, 2));
+    RC(sd_read_scalars(ctx, 0, 2, s));
+    E0 = s[0];
+    if (!have_ab) {                                                                         // :212-214 (the recursion's sector)
+      double Emin, Emax;
+      RC(energy_bounds_core(op, 80, nullptr, nullptr, true, seed, &Emin, &Emax));
+      sd_kpm_rescaling_from_bounds(Emin, Emax, &a, &b);
     }
+    mu.resize(kpm_m); g.resize(kpm_m);
+    sd_kpm_kernel(kpm_m, kernel, g.data());
+    return SD_OK;
   }
-  for (int iq = 0; iq < Qn; ++iq) {                                                       // :218 (serial over q)
-    double *Srow = Smat + (size_t)iq * W;
-    if (same_as[iq] >= 0) {
-      std::memcpy(Srow, Smat + (size_t)same_as[iq] * W, sizeof(double) * (size_t)W);
-      continue;
-    }
-    RC(sd_launch_szq(ctx, m, SD_C128, psic.p, q[iq], phi.p));                             // :223
-    const double norm_phi = norm_dev(op, phi.p, 2 * n, &rc); RC(rc);
-    if (norm_phi == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }       // :226-229
-    RC(sd_k_scale_div(ctx, phi.p, phi.p, 2 * n, norm_phi));                               // :231
-    RC(moments_dev(op, phi.p, kpm_m, a, b, mu.data()));
-    for (int k = 0; k < kpm_m; ++k) mu[k] *= g[k];                                        // :53
-    sd_kpm_reconstruct(mu.data(), kpm_m, omega, W, a, b, E0, Srow);
+  // Launch-bound sizes: the momenta's vectors share their launches (moments_dev_batched): five batches of vectors (phi + the
+  // recursion's three + nothing else) within 4 GiB, vectors of at most 2^22 rows.  sd_ctx_set_q_batch(ctx, 0): one momentum at a time.
+  bool can_batch(int Qb) const override {
+    const sd_model *m = op.m;
+    return batchable && op.ctx->q_batch && Qb >= 2 && m->nranks == 1 && !op.ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 16384 &&
+           op.n <= ((int64_t)1 << 22) && (int64_t)Qb * op.n * 16 * 4 <= ((int64_t)4 << 30);
+  }
+  void row(double *muk, double norm_phi, double *Srow) const {
+    for (int k = 0; k < kpm_m; ++k) muk[k] *= g[k];                                         // :53
+    sd_kpm_reconstruct(muk, kpm_m, omega, W, a, b, E0, Srow);
     const double n2 = norm_phi * norm_phi;
-    for (int iw = 0; iw < W; ++iw) Srow[iw] *= n2;                                        // :252
+    for (int iw = 0; iw < W; ++iw) Srow[iw] *= n2;                                          // :252
   }
+  int one(double *phi, double norm_phi, double *Srow) override {
+    RC(moments_dev(op, phi, kpm_m, a, b, mu.data()));
+    row(mu.data(), norm_phi, Srow);
+    return SD_OK;
+  }
+  int batch(double *phib, int Qk, const double *norms, double *const *rows) override {
+    std::vector<double> mub((size_t)Qk * (size_t)kpm_m);
+    std::vector<char> okv;
+    RC(moments_dev_batched(op, phib, Qk, kpm_m, a, b, mub.data(), okv));
+    for (int k = 0; k < Qk; ++k) {
+      double *muk = mub.data() + (size_t)k * (size_t)kpm_m;
+      if (!okv[k]) RC(moments_dev(op, phib + 2 * op.n * k, kpm_m, a, b, muk));              // the guard fired: the reference's loop
+      row(muk, norms[k], rows[k]);
+    }
+    return SD_OK;
+  }
+};
+
+struct LanczosSpectrum : Spectrum {
+  int lanc_m; double eta; int broaden, mm = 1;
+  std::vector<double> alpha, beta;
+  LanczosSpectrum(Op &o, const double *om, int w, int lanc_m_, double eta_, int broaden_)
+      : Spectrum(o, om, w), lanc_m(lanc_m_), eta(eta_), broaden(broaden_) {}
+  int check() const override {
+    if (broaden != SD_BROADEN_LORENTZ && broaden != SD_BROADEN_GAUSS) return sd_set_err(op.ctx, SD_EARG, "unknown broadening");
+    return lanc_m < 1 ? sd_set_err(op.ctx, SD_EARG, "lanc_m must be >= 1") : SD_OK;
+  }
+  int start(Op &os, const double *psic, double *scratch) override {
+    sd_ctx *ctx = os.ctx;
+    RC(plain_op(ctx, os.m, SD_C128, scratch, psic));                                        // src/LanczosSqw.jl:58
+    // E0 = real(dot(conj(psi0c), tmp)) (sic, :59): dot conjugates its first argument again, so this is Re sum psi_i*tmp_i,
+    // the product sum WITHOUT conjugation (equal to <psi|H|psi> for a real psi0).  Reduced on the device.
+    RC(sd_k_dotu(ctx, psic, scratch, os.n, 4));
+    double s[2]; RC(sd_read_scalars(ctx, 4, 2, s));
+    E0 = s[0];
+    mm = (int)std::max<int64_t>(std::min<int64_t>(lanc_m, op.n), 1);
+    alpha.resize(mm); beta.resize(mm);
+    return SD_OK;
+  }
+  // launch-bound sizes: all momenta in one recursion (src/LanczosSqw.jl:65 threads over them)
+  bool can_batch(int Qb) const override { return batchable && op.ctx->q_batch && Qb >= 2 && lanczos_fused_ok(op, Qb); }
+  int row(int m_eff, double norm_phi, double *Srow) const {
+    int rs = sd_spectral_from_tridiagonal(alpha.data(), beta.data(), m_eff, norm_phi, E0, omega, W, eta, broaden, Srow);
+    return rs ? sd_set_err(op.ctx, rs, "spectral_from_tridiagonal failed") : SD_OK;
+  }
+  int one(double *phi, double norm_phi, double *Srow) override {
+    int m_eff = 0;
+    RC(tridiag_dev(op, phi, lanc_m, 1e-12, alpha.data(), beta.data(), &m_eff));             // :73
+    return row(m_eff, norm_phi, Srow);
+  }
+  int batch(double *phib, int Qk, const double *norms, double *const *rows) override {
+    std::vector<double> al, be;
+    RC(lanczos_fused(op, Qk, phib, mm, 1, 0, 1e-12, al, be));                               // :73
+    for (int k = 0; k < Qk; ++k) {
+      int m_eff = 0;
+      tridiag_trim(mm, 1e-12, al.data() + (size_t)k * mm, be.data() + (size_t)k * mm, alpha.data(), beta.data(), &m_eff);
+      RC(row(m_eff, norms[k], rows[k]));
+    }
+    return SD_OK;
+  }
+};
+
+// The one S(q,w) driver.  psi0 (host vector, or device rows when on_dev) lives in the sector of `os`; make_phi(psic, q, out)
+// writes phi_q = O_q psi0 (ComplexF64) into the sector of sp.op, where sp turns it into the row S(q, .) of Smat (Qn x W).
+template <class MakePhi>
+int sqw_core(Op &os, int dtype, const void *psi0, bool on_dev, int64_t n, const MakePhi &make_phi, Spectrum &sp, const double *q,
+             int Qn, double *Smat) {
+  sd_ctx *ctx = os.ctx;
+  const int W = sp.W;
+  const int64_t nd = sp.op.n;
+  if (n != os.n) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the (local) basis dimension of its sector");
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  RC(sp.check());
+  if (!psi0 || !Smat || (Qn > 0 && !q) || (W > 0 && !sp.omega)) return sd_set_err(ctx, SD_EARG, "null argument");
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  DBuf psic, phi;
+  RC(psic.alloc(ctx, 2 * n)); RC(phi.alloc(ctx, 2 * n));
+  {
+    DBuf in;
+    const double *inp = (const double *)psi0;
+    if (!on_dev) { RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi0, nc * n)); inp = in.p; }
+    RC(sd_k_promote(ctx, psic.p, inp, nc, n));                                            // :202
+  }
+  // phi doubles as the scratch for H psi0 (only E0 is kept): the recursion then holds psi0, phi and its three work vectors --
+  // five vectors of n elements plus halo and send buffer on a shard
+  RC(sp.start(os, psic.p, phi.p));
+  if (nd != n) RC(phi.alloc(ctx, 2 * nd));                                                // phi_q lives in the recursion's sector
+  // every pair (q, 2 pi - q) of the list is computed once for a real psi0 (pair_momenta)
+  std::vector<int> same_as, live;
+  RC(pair_momenta(os, dtype, psic.p, n, q, Qn, same_as));
+  for (int iq = 0; iq < Qn; ++iq) if (same_as[iq] < 0) live.push_back(iq);
+  const int Qb = (int)live.size();
+  if (sp.can_batch(Qb)) {
+    DBuf phib, nrm;
+    RC(phib.alloc(ctx, 2 * nd * Qb)); RC(nrm.alloc(ctx, 2 * (int64_t)Qb));
+    for (int k = 0; k < Qb; ++k) {
+      RC(make_phi(psic.p, q[live[k]], phib.p + 2 * nd * k));                              // :223
+      RC(sd_k_nrm2sq_to(ctx, phib.p + 2 * nd * k, 2 * nd, nrm.p + 2 * k));
+    }
+    std::vector<double> hn(2 * (size_t)Qb);
+    SD_HIP(ctx, hipMemcpyAsync(hn.data(), nrm.p, sizeof(double) * hn.size(), hipMemcpyDeviceToHost, ctx->stream));
+    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // zero vectors (:226-229) drop out of the batch; the rest are normalised in place (:231)
+    std::vector<double *> kept; std::vector<double> norms;
+    for (int k = 0; k < Qb; ++k) {
+      const double nphi = std::sqrt(hn[2 * (size_t)k]);
+      double *Srow = Smat + (size_t)live[k] * W;
+      if (nphi == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }
+      const int dst = (int)kept.size();
+      if (dst != k) RC(d2d(ctx, phib.p + 2 * nd * dst, phib.p + 2 * nd * k, 2 * nd));
+      RC(sd_k_scale_div(ctx, phib.p + 2 * nd * dst, phib.p + 2 * nd * dst, 2 * nd, nphi));
+      kept.push_back(Srow); norms.push_back(nphi);
+    }
+    if (!kept.empty()) RC(sp.batch(phib.p, (int)kept.size(), norms.data(), kept.data()));
+  } else {
+    int rc = 0;
+    for (int iq : live) {                                                                 // :218 (serial over q)
+      double *Srow = Smat + (size_t)iq * W;
+      RC(make_phi(psic.p, q[iq], phi.p));                                                 // :223
+      const double norm_phi = norm_dev(sp.op, phi.p, 2 * nd, &rc); RC(rc);
+      if (norm_phi == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }     // :226-229, src/LanczosSqw.jl:67-70
+      RC(sd_k_scale_div(ctx, phi.p, phi.p, 2 * nd, norm_phi));                            // :231
+      RC(sp.one(phi.p, norm_phi, Srow));
+    }
+  }
+  for (int iq = 0; iq < Qn; ++iq)
+    if (same_as[iq] >= 0) std::memcpy(Smat + (size_t)iq * W, Smat + (size_t)same_as[iq] * W, sizeof(double) * (size_t)W);
   SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SD_OK;
 }
 
-static int sd_kpm_sqw_impl(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const double *q, int Qn,
-                          const double *omega, int W, int have_ab, double a, double b, int kpm_m, int kernel,
-                          uint64_t seed, double *Smat) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  return kpm_sqw_core(op, dtype, psi0, false, n, q, Qn, omega, W, have_ab, a, b, kpm_m, kernel, seed, Smat);
-}
-extern "C" int sd_kpm_sqw(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const double *q, int Qn,
-                          const double *omega, int W, int have_ab, double a, double b, int kpm_m, int kernel,
-                          uint64_t seed, double *Smat) {
-  SD_ABI_GUARD(ctx, sd_kpm_sqw_impl(ctx, m, dtype, psi0, n, q, Qn, omega, W, have_ab, a, b, kpm_m, kernel, seed, Smat));
-}
-
-static int sd_kpm_sqw_sharded_impl(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int dtype, const void *psi0_dev,
-                                  int64_t n_local, const double *q, int Qn, const double *omega, int W, int have_ab, double a,
-                                  double b, int kpm_m, int kernel, uint64_t seed, double *Smat) {
-  Op op; RC(op.init(ctx, m, comm));
-  return kpm_sqw_core(op, dtype, psi0_dev, true, n_local, q, Qn, omega, W, have_ab, a, b, kpm_m, kernel, seed, Smat);
-}
-extern "C" int sd_kpm_sqw_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int dtype, const void *psi0_dev,
-                                  int64_t n_local, const double *q, int Qn, const double *omega, int W, int have_ab, double a,
-                                  double b, int kpm_m, int kernel, uint64_t seed, double *Smat) {
-  SD_ABI_GUARD(ctx, sd_kpm_sqw_sharded_impl(ctx, m, comm, dtype, psi0_dev, n_local, q, Qn, omega, W, have_ab, a, b, kpm_m, kernel, seed, Smat));
-}
-
-static int sd_lanczos_sqw_impl(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const double *q,
-                              int Qn, const double *omega, int W, int lanc_m, double eta, int broaden, double *Smat) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
-  if (broaden != SD_BROADEN_LORENTZ && broaden != SD_BROADEN_GAUSS) return sd_set_err(ctx, SD_EARG, "unknown broadening");
-  if (lanc_m < 1) return sd_set_err(ctx, SD_EARG, "lanc_m must be >= 1");
-  const int nc = dtype == SD_C128 ? 2 : 1;
-  DBuf in, psic, tmp, phi;
-  RC(in.alloc(ctx, nc * n)); RC(psic.alloc(ctx, 2 * n)); RC(tmp.alloc(ctx, 2 * n)); RC(phi.alloc(ctx, 2 * n));
-  RC(h2d(ctx, in.p, psi0, nc * n));
-  RC(sd_k_promote(ctx, psic.p, in.p, nc, n));
-  RC(plain_op(ctx, m, SD_C128, tmp.p, psic.p));                                           // src/LanczosSqw.jl:58
-  // E0 = real(dot(conj(psi0c), tmp)) (sic, :59): dot conjugates its first argument again, so this is Re sum psi_i*tmp_i,
-  // the product sum WITHOUT conjugation (equal to <psi|H|psi> for a real psi0).  Reduced on the device.
-  RC(sd_k_dotu(ctx, psic.p, tmp.p, n, 4));
-  double e0s[2]; RC(sd_read_scalars(ctx, 4, 2, e0s));
-  const double E0 = e0s[0];
-  const int mm = (int)std::min<int64_t>(lanc_m, n);
-  std::vector<double> alpha(mm), beta(std::max(mm, 1));
-  int rc = 0;
-  std::vector<int> same_as;
-  RC(pair_momenta(op, dtype, psic.p, n, q, Qn, same_as));      // real psi0: the Lanczos coefficients of q and 2 pi - q agree
-  {   // launch-bound sizes: all momenta in one recursion (src/LanczosSqw.jl:65 threads over them)
-    std::vector<int> live;
-    for (int iq = 0; iq < Qn; ++iq) if (same_as[iq] < 0) live.push_back(iq);
-    const int Qb = (int)live.size();
-    if (ctx->q_batch && Qb >= 2 && lanczos_fused_ok(op, Qb)) {
-      DBuf phib, nrm;
-      RC(phib.alloc(ctx, 2 * n * Qb)); RC(nrm.alloc(ctx, 2 * (int64_t)Qb));
-      for (int k = 0; k < Qb; ++k) {
-        RC(sd_launch_szq(ctx, m, SD_C128, psic.p, q[live[k]], phib.p + 2 * n * k));
-        RC(sd_k_nrm2sq_to(ctx, phib.p + 2 * n * k, 2 * n, nrm.p + 2 * k));
-      }
-      std::vector<double> hn(2 * (size_t)Qb);
-      SD_HIP(ctx, hipMemcpyAsync(hn.data(), nrm.p, sizeof(double) * hn.size(), hipMemcpyDeviceToHost, ctx->stream));
-      SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      std::vector<int> kept; std::vector<double> norms;
-      for (int k = 0; k < Qb; ++k) {
-        const double nphi = std::sqrt(hn[2 * (size_t)k]);
-        double *Srow = Smat + (size_t)live[k] * W;
-        if (nphi == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }       // :67-70
-        const int dst = (int)kept.size();
-        if (dst != k) RC(d2d(ctx, phib.p + 2 * n * dst, phib.p + 2 * n * k, 2 * n));
-        RC(sd_k_scale_div(ctx, phib.p + 2 * n * dst, phib.p + 2 * n * dst, 2 * n, nphi));
-        kept.push_back(live[k]); norms.push_back(nphi);
-      }
-      const int Qk = (int)kept.size();
-      if (Qk > 0) {
-        std::vector<double> al, be;
-        RC(lanczos_fused(op, Qk, phib.p, mm, 1, 0, 1e-12, al, be));                       // :73
-        for (int k = 0; k < Qk; ++k) {
-          int m_eff = 0;
-          tridiag_trim(mm, 1e-12, al.data() + (size_t)k * mm, be.data() + (size_t)k * mm, alpha.data(), beta.data(), &m_eff);
-          int rs = sd_spectral_from_tridiagonal(alpha.data(), beta.data(), m_eff, norms[k], E0, omega, W, eta, broaden,
-                                                Smat + (size_t)kept[k] * W);
-          if (rs) return sd_set_err(ctx, rs, "spectral_from_tridiagonal failed");
-        }
-      }
-      for (int iq = 0; iq < Qn; ++iq)
-        if (same_as[iq] >= 0) std::memcpy(Smat + (size_t)iq * W, Smat + (size_t)same_as[iq] * W, sizeof(double) * (size_t)W);
-      return SD_OK;
-    }
-  }
-  for (int iq = 0; iq < Qn; ++iq) {
-    double *Srow = Smat + (size_t)iq * W;
-    if (same_as[iq] >= 0) { std::memcpy(Srow, Smat + (size_t)same_as[iq] * W, sizeof(double) * (size_t)W); continue; }
-    RC(sd_launch_szq(ctx, m, SD_C128, psic.p, q[iq], phi.p));
-    const double normv = norm_dev(op, phi.p, 2 * n, &rc); RC(rc);
-    if (normv == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }          // :67-70
-    RC(sd_k_scale_div(ctx, phi.p, phi.p, 2 * n, normv));
-    int m_eff = 0;
-    RC(tridiag_dev(op, phi.p, lanc_m, 1e-12, alpha.data(), beta.data(), &m_eff));     // :73
-    int rs = sd_spectral_from_tridiagonal(alpha.data(), beta.data(), m_eff, normv, E0, omega, W, eta, broaden, Srow);
-    if (rs) return sd_set_err(ctx, rs, "spectral_from_tridiagonal failed");
-  }
-  return SD_OK;
-}
-extern "C" int sd_lanczos_sqw(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const double *q,
-                              int Qn, const double *omega, int W, int lanc_m, double eta, int broaden, double *Smat) {
-  SD_ABI_GUARD(ctx, sd_lanczos_sqw_impl(ctx, m, dtype, psi0, n, q, Qn, omega, W, lanc_m, eta, broaden, Smat));
+// phi_q = S^z_q psi0 in psi0's own sector (src/KPM_Sqw.jl:223)
+auto szq_of(sd_ctx *ctx, const sd_model *m) {
+  return [=](const double *psic, double q, double *out) { return sd_launch_szq(ctx, m, SD_C128, psic, q, out); };
 }
 
 // ---- transverse S(q,w): S^+- and S^-+ between adjacent sectors (DESIGN.md "Transverse S(q,w)") ----
 // The caller owns both models: src holds psi0, dst is the sector S^-_q (op SD_SPIN_MINUS) or S^+_q (SD_SPIN_PLUS) maps it to.
-// E0 comes from src, the recursion (bounds, moments, tridiagonal) runs on dst's H.
-namespace {
+// E0 comes from src, the recursion (bounds, moments, tridiagonal) runs on dst's H.  H is real in both sectors, so the rows
+// of q and 2 pi - q agree for a real psi0 here too.
+auto spm_q_of(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op) {
+  return [=](const double *psic, double q, double *out) { return sd_launch_spm_q(ctx, src, dst, op, SD_C128, psic, q, out); };
+}
 template <class T>
 bool same_bits(const std::vector<T> &x, const std::vector<T> &y) {
   return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), sizeof(T) * x.size()) == 0);
@@ -1439,35 +1293,9 @@ int spm_check(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op) {
   return SD_OK;
 }
 
-// the source sector's part of the S(q,w) drivers: psi0 promoted to ComplexF64 on the device (psic, 2 n doubles) and the
-// unconjugated sum Re sum psi_i (H psi)_i (lanczos) or <psi0|H psi0> (kpm), as the zz drivers form them
-int transverse_source(Op &os, int dtype, const void *psi0, int64_t n, bool lanczos, DBuf &psic, double *E0) {
-  sd_ctx *ctx = os.ctx;
-  const int nc = dtype == SD_C128 ? 2 : 1;
-  RC(psic.alloc(ctx, 2 * n));
-  DBuf in, tmp;
-  RC(in.alloc(ctx, nc * n));
-  RC(h2d(ctx, in.p, psi0, nc * n));
-  RC(sd_k_promote(ctx, psic.p, in.p, nc, n));
-  in.release();
-  RC(tmp.alloc(ctx, 2 * n));
-  double s[2];
-  if (lanczos) {
-    RC(plain_op(ctx, os.m, SD_C128, tmp.p, psic.p));                                      // src/LanczosSqw.jl:58-59
-    RC(sd_k_dotu(ctx, psic.p, tmp.p, n, 4));
-    RC(sd_read_scalars(ctx, 4, 2, s));
-  } else {
-    sd_epi_args ea;
-    RC(os.apply(SD_C128, tmp.p, psic.p, SD_EPI_DOT, ea));                                 // src/KPM_Sqw.jl:208-209
-    RC(sd_read_scalars(ctx, 0, 2, s));
-  }
-  *E0 = s[0];
-  return SD_OK;
-}
-}  // namespace
-
-static int sd_spm_q_impl(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0,
-                         int64_t n_src, double q, void *phi, int64_t n_dst, bool on_dev) {
+// phi = S^-+_q psi0 as a vector (host pointers, or device pointers when on_dev)
+int spm_q_core(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0, int64_t n_src,
+               double q, void *phi, int64_t n_dst, bool on_dev) {
   RC(spm_check(ctx, src, dst, op));
   if (!psi0 || !phi) return sd_set_err(ctx, SD_EARG, "null argument");
   if (dtype_in != SD_F64 && dtype_in != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
@@ -1482,103 +1310,59 @@ static int sd_spm_q_impl(sd_ctx *ctx, const sd_model *src, const sd_model *dst, 
   RC(sd_launch_spm_q(ctx, src, dst, op, dtype_in, in.p, q, out.p));
   return d2h(ctx, phi, out.p, 2 * n_dst);
 }
+}  // namespace
+
+// kpm_sqw; psi0: host vector (unsharded form) or this rank's rows on the device (sharded form)
+extern "C" int sd_kpm_sqw(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const double *q, int Qn,
+                          const double *omega, int W, int have_ab, double a, double b, int kpm_m, int kernel,
+                          uint64_t seed, double *Smat) { return abi_guard(ctx, [&]() -> int {
+  Op op; RC(op.init(ctx, m, nullptr));
+  KpmSpectrum sp(op, omega, W, have_ab, a, b, kpm_m, kernel, seed);
+  return sqw_core(op, dtype, psi0, false, n, szq_of(ctx, m), sp, q, Qn, Smat);
+}); }
+
+extern "C" int sd_kpm_sqw_sharded(sd_ctx *ctx, const sd_model *m, sd_comm *comm, int dtype, const void *psi0_dev,
+                                  int64_t n_local, const double *q, int Qn, const double *omega, int W, int have_ab, double a,
+                                  double b, int kpm_m, int kernel, uint64_t seed, double *Smat) { return abi_guard(ctx, [&]() -> int {
+  Op op; RC(op.init(ctx, m, comm));
+  KpmSpectrum sp(op, omega, W, have_ab, a, b, kpm_m, kernel, seed);
+  return sqw_core(op, dtype, psi0_dev, true, n_local, szq_of(ctx, m), sp, q, Qn, Smat);
+}); }
+
+extern "C" int sd_lanczos_sqw(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const double *q, int Qn,
+                              const double *omega, int W, int lanc_m, double eta, int broaden, double *Smat) { return abi_guard(ctx, [&]() -> int {
+  Op op; RC(op.init(ctx, m, nullptr));
+  LanczosSpectrum sp(op, omega, W, lanc_m, eta, broaden);
+  return sqw_core(op, dtype, psi0, false, n, szq_of(ctx, m), sp, q, Qn, Smat);
+}); }
+
 extern "C" int sd_spm_q(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0_host,
                         int64_t n_src, double q, void *phi_out_host, int64_t n_dst) {
-  SD_ABI_GUARD(ctx, sd_spm_q_impl(ctx, src, dst, op, dtype_in, psi0_host, n_src, q, phi_out_host, n_dst, false));
+  return abi_guard(ctx, [&]() -> int { return spm_q_core(ctx, src, dst, op, dtype_in, psi0_host, n_src, q, phi_out_host, n_dst, false); });
 }
 extern "C" int sd_spm_q_dev(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0_dev,
                             int64_t n_src, double q, void *phi_out_dev, int64_t n_dst) {
-  SD_ABI_GUARD(ctx, sd_spm_q_impl(ctx, src, dst, op, dtype_in, psi0_dev, n_src, q, phi_out_dev, n_dst, true));
+  return abi_guard(ctx, [&]() -> int { return spm_q_core(ctx, src, dst, op, dtype_in, psi0_dev, n_src, q, phi_out_dev, n_dst, true); });
 }
 
-// kpm_sqw with phi = S^-+_q psi0: the loop of kpm_sqw_core's one-momentum-at-a-time path, the recursion on dst
-static int sd_kpm_sqw_transverse_impl(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype, const void *psi0,
-                                      int64_t n, const double *q, int Qn, const double *omega, int W, int have_ab, double a,
-                                      double b, int kpm_m, int kernel, uint64_t seed, double *Smat) {
-  RC(spm_check(ctx, src, dst, op));
-  Op os; RC(os.init(ctx, src, nullptr));
-  Op od; RC(od.init(ctx, dst, nullptr));
-  if (n != src->N) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the source basis dimension");
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
-  if (kpm_m < 2) return sd_set_err(ctx, SD_EARG, "kpm_m must be >= 2");
-  if (!psi0 || !Smat || (Qn > 0 && !q) || (W > 0 && !omega)) return sd_set_err(ctx, SD_EARG, "null argument");
-  const int64_t nd = dst->N;
-  DBuf psic, phi;
-  double E0 = 0.0;
-  RC(transverse_source(os, dtype, psi0, n, false, psic, &E0));
-  if (!have_ab) {                                                                         // the target sector's bounds
-    double Emin, Emax;
-    RC(energy_bounds_core(od, 80, nullptr, nullptr, true, seed, &Emin, &Emax));
-    sd_kpm_rescaling_from_bounds(Emin, Emax, &a, &b);
-  }
-  std::vector<double> mu(kpm_m), g(kpm_m);
-  sd_kpm_kernel(kpm_m, kernel, g.data());
-  std::vector<int> same_as;   // H is real in both sectors: phi_{2pi-q} = conj(phi_q) for a real psi0
-  RC(pair_momenta(os, dtype, psic.p, n, q, Qn, same_as));
-  RC(phi.alloc(ctx, 2 * nd));
-  int rc = 0;
-  for (int iq = 0; iq < Qn; ++iq) {
-    double *Srow = Smat + (size_t)iq * W;
-    if (same_as[iq] >= 0) { std::memcpy(Srow, Smat + (size_t)same_as[iq] * W, sizeof(double) * (size_t)W); continue; }
-    RC(sd_launch_spm_q(ctx, src, dst, op, SD_C128, psic.p, q[iq], phi.p));
-    const double norm_phi = norm_dev(od, phi.p, 2 * nd, &rc); RC(rc);
-    if (norm_phi == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }       // src/KPM_Sqw.jl:226-229
-    RC(sd_k_scale_div(ctx, phi.p, phi.p, 2 * nd, norm_phi));
-    RC(moments_dev(od, phi.p, kpm_m, a, b, mu.data()));
-    for (int k = 0; k < kpm_m; ++k) mu[k] *= g[k];
-    sd_kpm_reconstruct(mu.data(), kpm_m, omega, W, a, b, E0, Srow);
-    const double n2 = norm_phi * norm_phi;
-    for (int iw = 0; iw < W; ++iw) Srow[iw] *= n2;
-  }
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
-}
 extern "C" int sd_kpm_sqw_transverse(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype, const void *psi0,
                                      int64_t n, const double *q, int Qn, const double *omega, int W, int have_ab, double a,
-                                     double b, int kpm_m, int kernel, uint64_t seed, double *Smat) {
-  SD_ABI_GUARD(ctx, sd_kpm_sqw_transverse_impl(ctx, src, dst, op, dtype, psi0, n, q, Qn, omega, W, have_ab, a, b, kpm_m, kernel,
-                                               seed, Smat));
-}
-
-// lanczos_sqw with phi = S^-+_q psi0: the loop of sd_lanczos_sqw_impl's one-momentum-at-a-time path, the recursion on dst
-static int sd_lanczos_sqw_transverse_impl(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype,
-                                          const void *psi0, int64_t n, const double *q, int Qn, const double *omega, int W,
-                                          int lanc_m, double eta, int broaden, double *Smat) {
+                                     double b, int kpm_m, int kernel, uint64_t seed, double *Smat) { return abi_guard(ctx, [&]() -> int {
   RC(spm_check(ctx, src, dst, op));
   Op os; RC(os.init(ctx, src, nullptr));
   Op od; RC(od.init(ctx, dst, nullptr));
-  if (n != src->N) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the source basis dimension");
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
-  if (broaden != SD_BROADEN_LORENTZ && broaden != SD_BROADEN_GAUSS) return sd_set_err(ctx, SD_EARG, "unknown broadening");
-  if (lanc_m < 1) return sd_set_err(ctx, SD_EARG, "lanc_m must be >= 1");
-  if (!psi0 || !Smat || (Qn > 0 && !q) || (W > 0 && !omega)) return sd_set_err(ctx, SD_EARG, "null argument");
-  const int64_t nd = dst->N;
-  DBuf psic, phi;
-  double E0 = 0.0;
-  RC(transverse_source(os, dtype, psi0, n, true, psic, &E0));
-  const int mm = (int)std::max<int64_t>(std::min<int64_t>(lanc_m, nd), 1);
-  std::vector<double> alpha(mm), beta(mm);
-  std::vector<int> same_as;
-  RC(pair_momenta(os, dtype, psic.p, n, q, Qn, same_as));
-  RC(phi.alloc(ctx, 2 * nd));
-  int rc = 0;
-  for (int iq = 0; iq < Qn; ++iq) {
-    double *Srow = Smat + (size_t)iq * W;
-    if (same_as[iq] >= 0) { std::memcpy(Srow, Smat + (size_t)same_as[iq] * W, sizeof(double) * (size_t)W); continue; }
-    RC(sd_launch_spm_q(ctx, src, dst, op, SD_C128, psic.p, q[iq], phi.p));
-    const double normv = norm_dev(od, phi.p, 2 * nd, &rc); RC(rc);
-    if (normv == 0) { for (int iw = 0; iw < W; ++iw) Srow[iw] = 0.0; continue; }          // src/LanczosSqw.jl:67-70
-    RC(sd_k_scale_div(ctx, phi.p, phi.p, 2 * nd, normv));
-    int m_eff = 0;
-    RC(tridiag_dev(od, phi.p, lanc_m, 1e-12, alpha.data(), beta.data(), &m_eff));
-    int rs = sd_spectral_from_tridiagonal(alpha.data(), beta.data(), m_eff, normv, E0, omega, W, eta, broaden, Srow);
-    if (rs) return sd_set_err(ctx, rs, "spectral_from_tridiagonal failed");
-  }
-  return SD_OK;
-}
+  KpmSpectrum sp(od, omega, W, have_ab, a, b, kpm_m, kernel, seed);
+  sp.batchable = false;      // one momentum at a time, as before: sharing launches here is a separate, measured change
+  return sqw_core(os, dtype, psi0, false, n, spm_q_of(ctx, src, dst, op), sp, q, Qn, Smat);
+}); }
+
 extern "C" int sd_lanczos_sqw_transverse(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype,
                                          const void *psi0, int64_t n, const double *q, int Qn, const double *omega, int W,
-                                         int lanc_m, double eta, int broaden, double *Smat) {
-  SD_ABI_GUARD(ctx, sd_lanczos_sqw_transverse_impl(ctx, src, dst, op, dtype, psi0, n, q, Qn, omega, W, lanc_m, eta, broaden,
-                                                   Smat));
-}
+                                         int lanc_m, double eta, int broaden, double *Smat) { return abi_guard(ctx, [&]() -> int {
+  RC(spm_check(ctx, src, dst, op));
+  Op os; RC(os.init(ctx, src, nullptr));
+  Op od; RC(od.init(ctx, dst, nullptr));
+  LanczosSpectrum sp(od, omega, W, lanc_m, eta, broaden);
+  sp.batchable = false;      // one momentum at a time, as before: sharing launches here is a separate, measured change
+  return sqw_core(os, dtype, psi0, false, n, spm_q_of(ctx, src, dst, op), sp, q, Qn, Smat);
+}); }
