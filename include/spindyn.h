@@ -259,6 +259,51 @@ int sd_lanczos_sqw_transverse(sd_ctx *ctx, const sd_model *src, const sd_model *
                               int64_t n, const double *q, int Qn, const double *omega, int W, int lanc_m, double eta,
                               int broaden, double *Smat_out);
 
+/* ---- site-resolved KPM correlations (the quantity of the reference's src/TimeEvolution/KPM.jl, kpm_correlation_matrix) ----
+ *   mu_n^{ij} = <psi0| S^z_i T_n(H~) S^z_j |psi0>,   C_ij(w) = <psi0| S^z_i delta(w - (H - E0)) S^z_j |psi0>,
+ * sites 1-based, r_i = i - 1 as in Sz_q_vector, psi0 properly conjugated (mu is complex; real for a real psi0).  One recursion
+ * from S^z_j psi0 gives the moments against ALL L sites i: each Chebyshev step projects v_n = T_n(H~) S^z_j psi0 onto the L
+ * vectors S^z_i psi0 in one pass.  Rescaling a, b (0.99 pad; estimated from `seed` when have_ab == 0), kernel g_n,
+ * E0 = Re<psi0|H psi0> and x = (w + E0 - b)/a are those of sd_kpm_sqw.  Unsharded models only (SD_EARG otherwise); a caller's
+ * operator (sd_ctx_set_apply_callback) is honoured.
+ *
+ * sd_site_project: out[2(i-1) .. +1] = (re, im) of sum_rows conj(bra[row]) s_i(row) ket[row], s_i = +-1/2, i = 1..L -- bra of
+ * `dtype_bra` (n elements, not promoted), ket ComplexF64 (n elements), out 2L host doubles.  One pass over both vectors, sums
+ * in a fixed order: the same call gives the same bits.  _dev: bra, ket device pointers; the call synchronises the stream. */
+int sd_site_project(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_host, const void *ket_c128_host, int64_t n,
+                    double *out);
+int sd_site_project_dev(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_dev, const void *ket_c128_dev, int64_t n,
+                        double *out);
+/* mu_out[((s * M + n) * L + (i-1)) * 2 .. +1] = (re, im) of mu_n^{i j_s}, j_s = sources[s] (1-based, ns of them), n = 0..M-1:
+ * v_0 = S^z_j psi0, v_1 = H~ v_0, v_n = 2 H~ v_{n-1} - v_{n-2}, a projection after each; M - 1 applies per source, queued without
+ * a host round trip and read back once.  Sources share their launches under the conditions of sd_ctx_set_q_batch (bit-identical
+ * to one source at a time).  SD_EARG: a source outside 1..L, M < 2, a sharded model, or sum |v_n|^2 not finite or above
+ * 1e6 sum |v_0|^2 (a, b do not contain the spectrum; sd_last_error names them).  _dev: psi0 is a device pointer. */
+int sd_kpm_site_moments(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, const int *sources, int ns,
+                        int M, double a, double b, double *mu_out);
+int sd_kpm_site_moments_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, const int *sources, int ns,
+                            int M, double a, double b, double *mu_out);
+/* sd_kpm_reconstruct without the clamp at zero (off-diagonal C_ij is signed):
+ * out[w] = (mu_0 + 2 sum_{n>=1} mu_n T_n(x)) / (a pi sqrt(1 - x^2)), 0 for |x| >= 1; moments already damped (host) */
+int sd_kpm_reconstruct_signed(const double *mu_damped, int kpm_m, const double *omega, int W, double a, double b, double E0,
+                              double *out);
+/* C_out[(((i-1) * ns + s) * W + w) * 2 .. +1] = (re, im) of C_{i j_s}(omega[w]): the damped moments reconstructed unclamped,
+ * Re and Im separately. */
+int sd_kpm_site_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, const int *sources,
+                             int ns, const double *omega, int W, int have_ab, double a, double b, int kpm_m, int kernel,
+                             uint64_t seed, double *C_out);
+/* S^zz(q, w) at every q of the list from the site moments: the rows sd_kpm_sqw returns, Smat_out Qn x W row-major.
+ * translation_invariant == 0: ns must be L and sources name every site once;
+ *   mu_n(q) = Re (1/L) sum_ij e^{-iq(r_i - r_j)} mu_n^{ij} -- any psi0, any boundary, L recursions for any number of momenta.
+ * translation_invariant != 0: ns must be 1; mu_n(q) = Re sum_i e^{-iq(r_i - r_j)} mu_n^{ij} from the one source j -- exact when
+ *   psi0 and H are invariant under the cyclic shift (the ground state of a periodic chain): M - 1 applies for ALL momenta.
+ *   *defect_out = max_{n,q} |Im sum_i ...| / (|psi0|^2 / 4), which vanishes for an invariant state (1e-14) and is O(0.1) for
+ *   a state that is not: the caller decides (the Python mirror raises above ti_tol).  defect_out may be NULL; it is 0 when
+ *   translation_invariant == 0. */
+int sd_kpm_sqw_sites(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, const double *q, int Qn,
+                     const double *omega, int W, const int *sources, int ns, int translation_invariant, int have_ab, double a,
+                     double b, int kpm_m, int kernel, uint64_t seed, double *Smat_out, double *defect_out);
+
 /* ---- observables and initial states (reference src/Observables.jl, src/InitialStates.jl) ---- */
 /* magnetization_per_site   src/Observables.jl:14-36 : mags_out[L] = <S^z_i> */
 int sd_magnetization(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, double *mags_out);

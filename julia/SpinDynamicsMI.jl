@@ -20,6 +20,7 @@ using Libdl
 
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
+       site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -300,7 +301,8 @@ end
 function dynamical_structure_factor(model::Model, ψ0::AbstractVector, q::AbstractVector, ω::AbstractVector;
                                     method::Symbol=:lanczos, component::Symbol=:zz, lanc_m::Int=200, eta::Float64=0.05,
                                     broaden::Symbol=:lorentz, a::Union{Nothing,Float64}=nothing, b::Union{Nothing,Float64}=nothing,
-                                    kpm_m::Int=200, kernel::Symbol=:jackson, seed::Integer=0)
+                                    kpm_m::Int=200, kernel::Symbol=:jackson, seed::Integer=0,
+                                    translation_invariant::Bool=false, source::Int=1, ti_tol::Float64=1e-6)
     q_list = Float64.(q); ω_range = Float64.(ω)
     x = eltype(ψ0) <: Complex ? Vector{ComplexF64}(ψ0) : Vector{Float64}(ψ0)
     S = Matrix{Float64}(undef, length(ω_range), length(q_list))      # C row-major (Qn x W) == Julia (W x Qn) column-major
@@ -308,6 +310,7 @@ function dynamical_structure_factor(model::Model, ψ0::AbstractVector, q::Abstra
         # transverse spectra: S^{+-} (:pm), S^{-+} (:mp), S^{xx} = S^{yy} = (S^{+-} + S^{-+}) / 4 (:xx)
         ops = component === :pm ? (2,) : component === :mp ? (1,) : component === :xx ? (2, 1) :
               throw(ArgumentError("unknown component: $component; expected :zz, :pm, :mp or :xx"))
+        method === :kpm_sites && throw(ArgumentError("method=:kpm_sites computes S^zz only (component=:zz)"))
         (method === :lanczos || method === :kpm) || throw(ArgumentError("unsupported dynamical structure-factor method: $method"))
         br = broaden === :lorentz ? 0 : broaden === :gauss ? 1 : error("unknown broadening: $broaden")
         have = a !== nothing && b !== nothing
@@ -315,6 +318,10 @@ function dynamical_structure_factor(model::Model, ψ0::AbstractVector, q::Abstra
         parts = [transverse_rows(model, x, q_list, ω_range, op, method, lanc_m, eta, br, have, a, b, kpm_m, kern, seed) for op in ops]
         S = length(parts) == 2 ? 0.25 .* (parts[1] .+ parts[2]) : parts[1]
         return permutedims(S)
+    end
+    if method === :kpm_sites                                           # S^zz from the site-resolved moments (kpm_sqw_sites)
+        return kpm_sqw_sites(x, model, q_list, ω_range; a=a, b=b, kpm_m=kpm_m, kernel=kernel, seed=seed,
+                             translation_invariant=translation_invariant, source=source, ti_tol=ti_tol)
     end
     if method === :lanczos
         br = broaden === :lorentz ? 0 : broaden === :gauss ? 1 : error("unknown broadening: $broaden")
@@ -334,6 +341,105 @@ function dynamical_structure_factor(model::Model, ψ0::AbstractVector, q::Abstra
         throw(ArgumentError("unsupported dynamical structure-factor method: $method"))
     end
     return permutedims(S)                                              # (length(q), length(ω)) as the reference returns
+end
+
+# ---- site-resolved KPM correlations (the quantity of the reference's src/TimeEvolution/KPM.jl) -------------------------
+# mu_n^{ij} = <psi0| S^z_i T_n(H~) S^z_j |psi0>: one recursion per source site j gives the moments against all L sites i.
+# C row-major arrays come back as Julia column-major arrays with the index order reversed.
+hostvec(ψ0::AbstractVector) = eltype(ψ0) <: Complex ? Vector{ComplexF64}(ψ0) : Vector{Float64}(ψ0)
+
+# out[i] = <bra| S^z_i |ket> for every site i (one pass over both vectors)
+function site_project(model::Model, bra::AbstractVector, ket::AbstractVector)
+    b = hostvec(bra); k = Vector{ComplexF64}(ket)
+    length(b) == length(k) || throw(DimensionMismatch("length(bra) != length(ket)"))
+    out = Vector{ComplexF64}(undef, model.L)
+    check(ccall((:sd_site_project, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(b)), b, k, length(k), out), model.ctx.h)
+    return out
+end
+
+# mu[i, n + 1, s] = mu_n^{i j_s}, j_s = sources[s] (1-based), n = 0..M-1
+function kpm_site_moments(ψ0::AbstractVector, model::Model, M::Int, a::Real, b::Real; sources=collect(1:model.L))
+    x = hostvec(ψ0); src = Cint.(sources)
+    mu = Array{ComplexF64}(undef, model.L, M, length(src))
+    check(ccall((:sd_kpm_site_moments, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cint}, Cint, Cint, Float64, Float64, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(x)), x, length(x), src, length(src), M, Float64(a), Float64(b), mu), model.ctx.h)
+    return mu
+end
+
+# the unclamped reconstruction (real damped moments)
+function kpm_reconstruct_signed(mu_damped::Vector{Float64}, ω::AbstractVector, a::Real, b::Real, E0::Real)
+    ω_range = Float64.(ω)
+    out = Vector{Float64}(undef, length(ω_range))
+    check(ccall((:sd_kpm_reconstruct_signed, libspindyn), Cint,
+                (Ptr{Float64}, Cint, Ptr{Float64}, Cint, Float64, Float64, Float64, Ptr{Float64}),
+                mu_damped, length(mu_damped), ω_range, length(ω_range), Float64(a), Float64(b), Float64(E0), out))
+    return out
+end
+
+# C[w, s, i] = <psi0| S^z_i delta(ω_w - (H - E0)) S^z_{j_s} |psi0>, not clamped (the reference's name; its defects are not
+# reproduced: DESIGN.md 13)
+function kpm_correlation_matrix(ψ0::AbstractVector, model::Model, ω::AbstractVector; sources=collect(1:model.L),
+                                a::Union{Nothing,Float64}=nothing, b::Union{Nothing,Float64}=nothing, kpm_m::Int=200,
+                                kernel::Symbol=:jackson, seed::Integer=0)
+    x = hostvec(ψ0); src = Cint.(sources); ω_range = Float64.(ω)
+    have = a !== nothing && b !== nothing
+    kern = kernel === :jackson ? 0 : kernel === :lorentz ? 1 : 2
+    Cm = Array{ComplexF64}(undef, length(ω_range), length(src), model.L)
+    check(ccall((:sd_kpm_site_correlations, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cint}, Cint, Ptr{Float64}, Cint, Cint, Float64, Float64, Cint,
+                 Cint, UInt64, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(x)), x, length(x), src, length(src), ω_range, length(ω_range), have,
+                have ? a : 0.0, have ? b : 0.0, kpm_m, kern, seed, Cm), model.ctx.h)
+    return Cm
+end
+
+# is the model unchanged by the cyclic shift i -> i + 1 (mod L)?
+function shift_invariant(model::Model)
+    L = model.L
+    function table(bonds)
+        t = Dict{Tuple{Int,Int},Float64}()
+        for (i, j, J) in bonds
+            i == j && continue
+            key = (min(i, j), max(i, j))
+            t[key] = get(t, key, 0.0) + J
+        end
+        return filter(kv -> kv.second != 0.0, t)
+    end
+    shifted(t) = Dict((min(mod1(i + 1, L), mod1(j + 1, L)), max(mod1(i + 1, L), mod1(j + 1, L))) => v for ((i, j), v) in t)
+    for bonds in (model.hopping_list, model.zz_list)
+        t = table(bonds)
+        shifted(t) == t || return false
+    end
+    return all(==(first(model.onsite_field)), model.onsite_field)
+end
+
+# S^zz(q, ω) from the site moments -> (length(q), length(ω)), the rows kpm_sqw returns.  translation_invariant=true: ONE
+# recursion from site `source` for all momenta (periodic chain, invariant ψ0); ArgumentError when the lists are not shift
+# invariant or the invariance defect the library returns exceeds ti_tol.
+function kpm_sqw_sites(ψ0::AbstractVector, model::Model, q::AbstractVector, ω::AbstractVector;
+                       a::Union{Nothing,Float64}=nothing, b::Union{Nothing,Float64}=nothing, kpm_m::Int=200,
+                       kernel::Symbol=:jackson, seed::Integer=0, translation_invariant::Bool=false, source::Int=1,
+                       ti_tol::Float64=1e-6)
+    x = hostvec(ψ0); q_list = Float64.(q); ω_range = Float64.(ω)
+    if translation_invariant
+        shift_invariant(model) || throw(ArgumentError("translation_invariant=true needs lists that the cyclic shift leaves unchanged"))
+    end
+    src = translation_invariant ? Cint[source] : Cint.(1:model.L)
+    have = a !== nothing && b !== nothing
+    kern = kernel === :jackson ? 0 : kernel === :lorentz ? 1 : 2
+    S = Matrix{Float64}(undef, length(ω_range), length(q_list))
+    defect = Ref{Float64}(0.0)
+    check(ccall((:sd_kpm_sqw_sites, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Float64}, Cint, Ptr{Float64}, Cint, Ptr{Cint}, Cint, Cint, Cint,
+                 Float64, Float64, Cint, Cint, UInt64, Ptr{Float64}, Ref{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(x)), x, length(x), q_list, length(q_list), ω_range, length(ω_range), src,
+                length(src), translation_invariant, have, have ? a : 0.0, have ? b : 0.0, kpm_m, kern, seed, S, defect), model.ctx.h)
+    if translation_invariant && !(defect[] <= ti_tol)
+        throw(ArgumentError("psi0 is not translation invariant: defect $(defect[]) > ti_tol $ti_tol"))
+    end
+    return permutedims(S)
 end
 
 end # module

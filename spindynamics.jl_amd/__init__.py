@@ -14,7 +14,8 @@ from .hamiltonian import (Sminus_q_vector, Splus_q_vector, Sz_q_vector, apply_H,
 from .solvers import (chebyshev_coeffs, chebyshev_time_evolve, compute_chebyshev_moments, estimate_energy_bounds,
                       get_kernel, get_rescaling_params, kpm_reconstruct, kpm_sqw, kpm_sqw_transverse, kpm_sw,
                       krylov_time_evolve, lanczos_extremal, lanczos_groundstate, lanczos_sqw, lanczos_sqw_transverse,
-                      lanczos_tridiag, rescaling_from_bounds, spectral_from_tridiagonal, symtridiag_eig)
+                      lanczos_tridiag, rescaling_from_bounds, spectral_from_tridiagonal, symtridiag_eig,
+                      kpm_correlation_matrix, kpm_reconstruct_signed, kpm_site_moments, kpm_sqw_sites, site_project)
 from .observables import connected_correlations, magnetization_per_site, structure_factor_Sq
 from . import initial_states
 from .initial_states import domain_wall_state, neel_state, polarized_state, polarized_state_with_flips

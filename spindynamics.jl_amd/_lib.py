@@ -133,6 +133,13 @@ PROTOTYPES = {
     "sd_spm_q_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _d, _vp, _i64]),
     "sd_kpm_sqw_transverse": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _dp, _i, _dp, _i, _i, _d, _d, _i, _i, _u64, _dp]),
     "sd_lanczos_sqw_transverse": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _dp, _i, _dp, _i, _i, _d, _i, _dp]),
+    "sd_site_project": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _dp]),
+    "sd_site_project_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _dp]),
+    "sd_kpm_site_moments": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _i, _d, _d, _dp]),
+    "sd_kpm_site_moments_dev": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _i, _d, _d, _dp]),
+    "sd_kpm_reconstruct_signed": (_i, [_dp, _i, _dp, _i, _d, _d, _d, _dp]),
+    "sd_kpm_site_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _dp, _i, _i, _d, _d, _i, _i, _u64, _dp]),
+    "sd_kpm_sqw_sites": (_i, [_vp, _vp, _i, _vp, _i64, _dp, _i, _dp, _i, _ip, _i, _i, _i, _d, _d, _i, _i, _u64, _dp, _dp]),
     "sd_magnetization": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),
     "sd_magnetization_dev": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),
     "sd_connected_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),

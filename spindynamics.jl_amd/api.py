@@ -52,7 +52,9 @@ def structure_factor(model, psi):
 def dynamical_structure_factor(model, psi0, q, omega, method="lanczos", component="zz", **kwargs):
     """dynamical_structure_factor(model, psi0, q, omega; method=:lanczos, kwargs...) -> S[len(q), len(omega)]
     -- src/PublicAPI.jl:122-155.  component="zz" is S^zz; "+-", "-+" and "xx" are the transverse spectra of
-    solvers.lanczos_sqw_transverse / kpm_sqw_transverse (intermediate states in the adjacent sectors)."""
+    solvers.lanczos_sqw_transverse / kpm_sqw_transverse (intermediate states in the adjacent sectors).
+    method="kpm_sites" (S^zz only) takes the moments of every momentum from site-resolved recursions
+    (solvers.kpm_sqw_sites: translation_invariant=True needs one recursion for all momenta)."""
     q_list = np.asarray(q, dtype=np.float64)
     w = np.asarray(omega, dtype=np.float64)
     if component != "zz":
@@ -62,9 +64,13 @@ def dynamical_structure_factor(model, psi0, q, omega, method="lanczos", componen
             return solvers.lanczos_sqw_transverse(psi0, model, q_list, w, component=component, **kwargs)
         if method == "kpm":
             return solvers.kpm_sqw_transverse(psi0, model, q_list, w, component=component, **kwargs)
+        if method == "kpm_sites":
+            raise ArgumentError("method=\"kpm_sites\" computes S^zz only (component=\"zz\")")
         raise ArgumentError(f"unsupported dynamical structure-factor method: {method}")
     if method == "lanczos":
         return solvers.lanczos_sqw(psi0, model, q_list, w, **kwargs)
     if method == "kpm":
         return solvers.kpm_sqw(psi0, model, q_list, w, **kwargs)
+    if method == "kpm_sites":
+        return solvers.kpm_sqw_sites(psi0, model, q_list, w, **kwargs)
     raise ArgumentError(f"unsupported dynamical structure-factor method: {method}")

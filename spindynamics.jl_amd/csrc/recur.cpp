@@ -1310,6 +1310,133 @@ int spm_q_core(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, in
   RC(sd_launch_spm_q(ctx, src, dst, op, dtype_in, in.p, q, out.p));
   return d2h(ctx, phi, out.p, 2 * n_dst);
 }
+// ---- site-resolved KPM moments (the quantity of the reference's src/TimeEvolution/KPM.jl) ----
+// mu_n^{ij} = <psi0| S^z_i T_n(H~) S^z_j |psi0> for the sources j = sources[0..ns) against ALL sites i: per source
+// v_0 = S^z_j psi0 (k_spin_op), v_1 = H~ v_0 (SD_EPI_RESCALE), v_n = 2 H~ v_{n-1} - v_{n-2} (SD_EPI_RECUR), and after each vector
+// one projection pass <S^z_i psi0|v_n>, i = 1..L (sd_launch_site_project) whose 2L + 2 doubles land in a slot of their own on the
+// device: the whole recursion is queued without a host round trip and read back once.  psi0: device, `dtype`, N rows -- the bra
+// stays in its own element type.  mu: ns x M x L complex (re, im).  Sources share their launches (sd_epi_args::batch) under
+// the conditions of KpmSpectrum::can_batch; a source of a batch sees the arithmetic of a recursion of its own.
+int site_moments_dev(Op &op, int dtype, const double *psi0, const int *sources, int ns, int M, double a, double b, double *mu) {
+  sd_ctx *ctx = op.ctx;
+  const sd_model *m = op.m;
+  const int64_t N = op.n;
+  const int L = m->L;
+  if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "site moments need an unsharded model");
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (M < 2) return sd_set_err(ctx, SD_EARG, "kpm_m must be >= 2");
+  if (ns < 1 || !sources) return sd_set_err(ctx, SD_EARG, "at least one source site is needed");
+  for (int s = 0; s < ns; ++s)
+    if (sources[s] < 1 || sources[s] > L) return sd_set_err(ctx, SD_EARG, "source site " + std::to_string(sources[s]) + " is outside 1..L");
+  if (!(a > 0.0) || !std::isfinite(a) || !std::isfinite(b)) return sd_set_err(ctx, SD_EARG, "the rescaling needs a finite a > 0 and a finite b");
+  if (!psi0 || !mu) return sd_set_err(ctx, SD_EARG, "null argument");
+  int Qmax = 1;
+  if (ctx->q_batch && ns >= 2 && !ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 16384 && N <= ((int64_t)1 << 22))
+    Qmax = (int)std::min<int64_t>(ns, std::max<int64_t>(1, ((int64_t)4 << 30) / (std::max<int64_t>(N, 1) * 16 * 4)));
+  const int64_t slot = 2 * (int64_t)L + 2, srow = slot * M;
+  DBuf psic, b0, b1, b2, res;
+  RC(psic.alloc(ctx, 2 * N));
+  RC(b0.alloc(ctx, 2 * N * Qmax)); RC(b1.alloc(ctx, 2 * N * Qmax)); RC(b2.alloc(ctx, 2 * N * Qmax));
+  RC(res.alloc(ctx, srow * ns));
+  RC(sd_k_promote(ctx, psic.p, psi0, dtype == SD_C128 ? 2 : 1, N));
+  for (int s0 = 0; s0 < ns; s0 += Qmax) {
+    const int Qb = std::min(Qmax, ns - s0);
+    double *v_prev = b0.p, *v_curr = b1.p, *v_next = b2.p;
+    double *r0 = res.p + srow * s0;
+    auto project = [&](const double *v, int n) {
+      return sd_launch_site_project(ctx, m, dtype, psi0, 0, v, N, Qb, r0 + slot * n, srow);
+    };
+    for (int k = 0; k < Qb; ++k) RC(sd_launch_spin_op(ctx, m, SD_C128, sources[s0 + k], SD_SPIN_Z, psic.p, v_prev + 2 * N * k));
+    RC(project(v_prev, 0));
+    sd_epi_args ea; ea.a = a; ea.b = b;
+    ea.batch = Qb; ea.bstride = N;
+    ctx->n_applies += Qb - 1;                                   // (Op::apply counts one)
+    RC(op.apply(SD_C128, v_curr, v_prev, SD_EPI_RESCALE, ea));
+    RC(project(v_curr, 1));
+    for (int n = 2; n <= M - 1; ++n) {
+      ea.prev = v_prev;
+      ctx->n_applies += Qb - 1;
+      RC(op.apply(SD_C128, v_next, v_curr, SD_EPI_RECUR, ea));
+      RC(project(v_next, n));
+      double *t = v_prev; v_prev = v_curr; v_curr = v_next; v_next = t;
+    }
+  }
+  std::vector<double> hs((size_t)(srow * ns));
+  SD_HIP(ctx, hipMemcpyAsync(hs.data(), res.p, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int s = 0; s < ns; ++s) {
+    const double *h = hs.data() + (size_t)(srow * s);
+    const double n0 = h[2 * L];
+    for (int n = 0; n < M; ++n) {
+      const double n2 = h[(size_t)(slot * n) + 2 * L];
+      if (!std::isfinite(n2) || n2 > 1e6 * n0)
+        return sd_set_err(ctx, SD_EARG, "the Chebyshev vectors grow (|v_" + std::to_string(n) + "|^2 = " + std::to_string(n2) + " from |v_0|^2 = " +
+                                            std::to_string(n0) + "): a = " + std::to_string(a) + ", b = " + std::to_string(b) +
+                                            " do not contain the spectrum");
+      std::memcpy(mu + ((size_t)s * M + n) * 2 * L, h + (size_t)(slot * n), sizeof(double) * 2 * (size_t)L);
+    }
+  }
+  return SD_OK;
+}
+
+// psi0 (host vector, or device rows when on_dev) on the device in its own element type
+int site_stage(sd_ctx *ctx, int dtype, const void *psi0, bool on_dev, int64_t n, DBuf &in, const double **dev) {
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (!psi0) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (on_dev) { *dev = (const double *)psi0; return SD_OK; }
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi0, nc * n));
+  *dev = in.p;
+  return SD_OK;
+}
+
+int site_project_core(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra, const void *ket, int64_t n, double *out,
+                      bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!ket || !out) return sd_set_err(ctx, SD_EARG, "null argument");
+  DBuf bin, kin, res;
+  const double *b = nullptr, *k = nullptr;
+  RC(site_stage(ctx, dtype_bra, bra, on_dev, n, bin, &b));
+  RC(site_stage(ctx, SD_C128, ket, on_dev, n, kin, &k));
+  const int L = m->L;
+  RC(res.alloc(ctx, 2 * (int64_t)L + 2));
+  RC(sd_launch_site_project(ctx, m, dtype_bra, b, 0, k, n, 1, res.p, 2 * (int64_t)L + 2));
+  SD_HIP(ctx, hipMemcpyAsync(out, res.p, sizeof(double) * 2 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+
+int site_moments_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const int *sources, int ns, int M,
+                      double a, double b, double *mu, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the basis dimension");
+  DBuf in;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi0, on_dev, n, in, &p));
+  return site_moments_dev(op, dtype, p, sources, ns, M, a, b, mu);
+}
+
+// E0, a, b and the damping factors exactly as kpm_sqw forms them (KpmSpectrum::start), then the site moments of a host psi0
+int site_spectral_moments(Op &op, KpmSpectrum &sp, int dtype, const void *psi0, int64_t n, const int *sources, int ns,
+                          std::vector<double> &mu) {
+  sd_ctx *ctx = op.ctx;
+  if (op.m->nranks != 1) return sd_set_err(ctx, SD_EARG, "site correlations need an unsharded model");
+  if (n != op.n) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the basis dimension");
+  RC(sp.check());
+  if (sp.W > 0 && !sp.omega) return sd_set_err(ctx, SD_EARG, "null argument");
+  DBuf in;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi0, false, n, in, &p));
+  {
+    DBuf psic, scratch;
+    RC(psic.alloc(ctx, 2 * n)); RC(scratch.alloc(ctx, 2 * n));
+    RC(sd_k_promote(ctx, psic.p, p, dtype == SD_C128 ? 2 : 1, n));
+    RC(sp.start(op, psic.p, scratch.p));
+  }
+  mu.assign((size_t)std::max(ns, 0) * (size_t)sp.kpm_m * (size_t)op.m->L * 2, 0.0);
+  return site_moments_dev(op, dtype, p, sources, ns, sp.kpm_m, sp.a, sp.b, mu.data());
+}
 }  // namespace
 
 // kpm_sqw; psi0: host vector (unsharded form) or this rank's rows on the device (sharded form)
@@ -1365,4 +1492,115 @@ extern "C" int sd_lanczos_sqw_transverse(sd_ctx *ctx, const sd_model *src, const
   LanczosSpectrum sp(od, omega, W, lanc_m, eta, broaden);
   sp.batchable = false;      // one momentum at a time, as before: sharing launches here is a separate, measured change
   return sqw_core(os, dtype, psi0, false, n, spm_q_of(ctx, src, dst, op), sp, q, Qn, Smat);
+}); }
+
+extern "C" int sd_site_project(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_host, const void *ket_host, int64_t n,
+                               double *out) {
+  return abi_guard(ctx, [&]() -> int { return site_project_core(ctx, m, dtype_bra, bra_host, ket_host, n, out, false); });
+}
+extern "C" int sd_site_project_dev(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_dev, const void *ket_dev, int64_t n,
+                                   double *out) {
+  return abi_guard(ctx, [&]() -> int { return site_project_core(ctx, m, dtype_bra, bra_dev, ket_dev, n, out, true); });
+}
+
+extern "C" int sd_kpm_site_moments(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, const int *sources,
+                                   int ns, int M, double a, double b, double *mu_out) {
+  return abi_guard(ctx, [&]() -> int { return site_moments_core(ctx, m, dtype, psi0_host, n, sources, ns, M, a, b, mu_out, false); });
+}
+extern "C" int sd_kpm_site_moments_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, const int *sources,
+                                       int ns, int M, double a, double b, double *mu_out) {
+  return abi_guard(ctx, [&]() -> int { return site_moments_core(ctx, m, dtype, psi0_dev, n, sources, ns, M, a, b, mu_out, true); });
+}
+
+extern "C" int sd_kpm_reconstruct_signed(const double *mu, int kpm_m, const double *omega, int W, double a, double b, double E0,
+                                         double *out) {
+  if (kpm_m < 1 || W < 0 || !mu || !out || (W > 0 && !omega)) return SD_EARG;
+  const double PI = 3.14159265358979323846;
+  for (int iw = 0; iw < W; ++iw) {
+    const double x = (omega[iw] + E0 - b) / a;
+    if (!(std::fabs(x) < 1.0)) { out[iw] = 0.0; continue; }
+    double tm = 1.0, tc = x, sum_val = mu[0];                          // T_0, T_1
+    for (int n = 1; n < kpm_m; ++n) {
+      sum_val += 2.0 * mu[n] * tc;
+      const double tn = 2.0 * x * tc - tm;
+      tm = tc; tc = tn;
+    }
+    out[iw] = sum_val / (a * (PI * std::sqrt(1.0 - x * x)));
+  }
+  return SD_OK;
+}
+
+extern "C" int sd_kpm_site_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const int *sources,
+                                        int ns, const double *omega, int W, int have_ab, double a, double b, int kpm_m, int kernel,
+                                        uint64_t seed, double *C_out) { return abi_guard(ctx, [&]() -> int {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (!C_out) return sd_set_err(ctx, SD_EARG, "null argument");
+  KpmSpectrum sp(op, omega, W, have_ab, a, b, kpm_m, kernel, seed);
+  std::vector<double> mu;
+  RC(site_spectral_moments(op, sp, dtype, psi0, n, sources, ns, mu));
+  const int L = m->L, M = kpm_m;
+  std::vector<double> mre(M), mim(M), cre(std::max(W, 1)), cim(std::max(W, 1));
+  for (int s = 0; s < ns; ++s)
+    for (int i = 0; i < L; ++i) {
+      for (int k = 0; k < M; ++k) {
+        const double *e = mu.data() + (((size_t)s * M + k) * L + i) * 2;
+        mre[k] = sp.g[k] * e[0]; mim[k] = sp.g[k] * e[1];
+      }
+      sd_kpm_reconstruct_signed(mre.data(), M, omega, W, sp.a, sp.b, sp.E0, cre.data());
+      sd_kpm_reconstruct_signed(mim.data(), M, omega, W, sp.a, sp.b, sp.E0, cim.data());
+      double *row = C_out + ((size_t)i * ns + s) * (size_t)W * 2;
+      for (int iw = 0; iw < W; ++iw) { row[2 * iw] = cre[iw]; row[2 * iw + 1] = cim[iw]; }
+    }
+  return SD_OK;
+}); }
+
+extern "C" int sd_kpm_sqw_sites(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const double *q, int Qn,
+                                const double *omega, int W, const int *sources, int ns, int translation_invariant, int have_ab,
+                                double a, double b, int kpm_m, int kernel, uint64_t seed, double *Smat,
+                                double *defect_out) { return abi_guard(ctx, [&]() -> int {
+  Op op; RC(op.init(ctx, m, nullptr));
+  const int L = m->L, M = kpm_m;
+  if (!Smat || (Qn > 0 && !q) || Qn < 0) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (ns < 1 || !sources) return sd_set_err(ctx, SD_EARG, "at least one source site is needed");
+  if (translation_invariant) {
+    if (ns != 1) return sd_set_err(ctx, SD_EARG, "translation_invariant takes exactly one source site");
+  } else {
+    if (ns != L) return sd_set_err(ctx, SD_EARG, "without translation_invariant the sources must be all L sites, each once");
+    std::vector<char> seen((size_t)L + 1, 0);
+    for (int s = 0; s < ns; ++s) {
+      if (sources[s] < 1 || sources[s] > L) return sd_set_err(ctx, SD_EARG, "source site " + std::to_string(sources[s]) + " is outside 1..L");
+      if (seen[sources[s]]++) return sd_set_err(ctx, SD_EARG, "without translation_invariant the sources must be all L sites, each once");
+    }
+  }
+  KpmSpectrum sp(op, omega, W, have_ab, a, b, kpm_m, kernel, seed);
+  std::vector<double> mu;
+  RC(site_spectral_moments(op, sp, dtype, psi0, n, sources, ns, mu));
+  double defect = 0.0;
+  const double quarter = mu[((size_t)0 * L + (sources[0] - 1)) * 2];          // mu_0^{jj} = |psi0|^2 / 4
+  std::vector<double> muq(M), cr(L), ci(L);
+  for (int iq = 0; iq < Qn; ++iq) {
+    for (int r = 0; r < L; ++r) { cr[r] = std::cos(q[iq] * (double)r); ci[r] = std::sin(q[iq] * (double)r); }
+    for (int k = 0; k < M; ++k) {
+      double sre = 0.0, sim = 0.0;
+      for (int s = 0; s < ns; ++s) {
+        const int rj = sources[s] - 1;
+        const double *e = mu.data() + ((size_t)s * M + k) * L * 2;
+        double tre = 0.0, tim = 0.0;                                          // sum_i e^{-iq r_i} mu^{ij}
+        for (int i = 0; i < L; ++i) { tre += cr[i] * e[2 * i] + ci[i] * e[2 * i + 1]; tim += cr[i] * e[2 * i + 1] - ci[i] * e[2 * i]; }
+        sre += cr[rj] * tre - ci[rj] * tim;                                   // times e^{+iq r_j}
+        sim += cr[rj] * tim + ci[rj] * tre;
+      }
+      if (translation_invariant) {
+        muq[k] = sre;
+        if (quarter > 0.0) defect = std::max(defect, std::fabs(sim) / quarter);
+        else if (sim != 0.0) defect = HUGE_VAL;
+      } else {
+        muq[k] = sre / (double)L;
+      }
+      muq[k] *= sp.g[k];
+    }
+    sd_kpm_reconstruct(muq.data(), M, omega, W, sp.a, sp.b, sp.E0, Smat + (size_t)iq * W);
+  }
+  if (defect_out) *defect_out = defect;
+  return SD_OK;
 }); }

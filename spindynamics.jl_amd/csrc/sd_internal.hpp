@@ -275,6 +275,12 @@ int sd_launch_szq(sd_ctx *ctx, const sd_model *m, int dtype_in, const void *psi0
 int sd_launch_spm_q(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, int dtype_in, const void *psi0, double q,
                     void *phi);
 
+// dst + k * dstride (k < batch): 2L + 2 doubles -- (re, im) of <bra| S^z_i |ket_k>, i = 1..L, then (sum |ket_k|^2, 0) -- from one
+// pass over bra (dtype_bra, not promoted) and ket_k = ket + k * bstride (ComplexF64); bra_bstride 0: one bra for the whole
+// batch.  Queued on the context's stream, deterministic (kernels_sites.hip)
+int sd_launch_site_project(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra, int64_t bra_bstride, const void *ket,
+                           int64_t bstride, int batch, double *dst, int64_t dstride);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.

@@ -312,6 +312,160 @@ def lanczos_sqw_transverse(psi0, model, q_list, omega, component="+-", lanc_m=20
     return _transverse(psi0, model, q_list, omega, component, run)
 
 
+# ---- site-resolved KPM correlations (the quantity of the reference's src/TimeEvolution/KPM.jl) ----
+_ip = C.POINTER(C.c_int)
+
+
+def _host_vec(x):
+    """psi0 as a host array and its dtype code; a torch tensor (host or device) is copied to the host."""
+    if _is_torch(x):
+        x = x.detach().cpu().numpy()
+    return _vec(x)
+
+
+def _sources(model, sources):
+    src = np.arange(1, model.L + 1) if sources is None else np.atleast_1d(np.asarray(sources))
+    if src.ndim != 1 or len(src) == 0 or not np.issubdtype(src.dtype, np.integer):
+        raise ArgumentError("sources must be a non-empty list of 1-based site indices")
+    return np.ascontiguousarray(src, dtype=np.int32)
+
+
+def site_project(model, bra, ket):
+    """out[i-1] = <bra| S^z_i |ket> = sum_rows conj(bra) s_i ket for every site i at once (one pass over both vectors, fixed
+    summation order) -> complex array of L entries.  bra: Float64 or ComplexF64 (used as it is); ket: ComplexF64.  numpy
+    arrays or torch device tensors (both of the same kind)."""
+    out = np.empty(model.L, dtype=np.complex128)
+    if _is_torch(bra) or _is_torch(ket):
+        import torch
+        if not (_is_torch(bra) and _is_torch(ket)):
+            raise ArgumentError("bra and ket must both be numpy arrays or both torch device tensors")
+        if bra.dtype not in (torch.float64, torch.complex128) or ket.dtype != torch.complex128:
+            raise ArgumentError("bra must be float64 or complex128 and ket complex128")
+        if len(bra) != len(ket):
+            raise DimensionMismatch("length(bra) != length(ket)")
+        _bind_torch_stream(model, bra)
+        _bind_torch_stream(model, ket)
+        check(lib().sd_site_project_dev(model.ctx.h, model.h, SD_C128 if bra.is_complex() else SD_F64, bra.data_ptr(),
+                                        ket.data_ptr(), len(ket), out.ctypes.data_as(_dp)), model.ctx.h)
+        return out
+    b, code = _vec(bra)
+    k = _c128(ket, len(b), "ket")
+    check(lib().sd_site_project(model.ctx.h, model.h, code, b.ctypes.data, k.ctypes.data, len(k), out.ctypes.data_as(_dp)),
+          model.ctx.h)
+    return out
+
+
+def kpm_site_moments(psi0, model, M, a, b, sources=None):
+    """mu[s, n, i-1] = <psi0| S^z_i T_n(H~) S^z_j |psi0>, j = sources[s] (1-based; None: all sites), n = 0..M-1, H~ = (H - b)/a
+    -> complex array (len(sources), M, L).  One recursion of M - 1 applies per source gives the moments against all L sites.
+    psi0: numpy array or torch device tensor (stays on the device)."""
+    src = _sources(model, sources)
+    mu = np.empty((len(src), int(M), model.L), dtype=np.complex128)
+    if _is_torch(psi0) and psi0.is_cuda:
+        import torch
+        if psi0.dtype not in (torch.float64, torch.complex128):
+            raise ArgumentError("vectors must be float64 or complex128")
+        _bind_torch_stream(model, psi0)
+        check(lib().sd_kpm_site_moments_dev(model.ctx.h, model.h, SD_C128 if psi0.is_complex() else SD_F64, psi0.data_ptr(),
+                                            len(psi0), src.ctypes.data_as(_ip), len(src), int(M), float(a), float(b),
+                                            mu.ctypes.data_as(_dp)), model.ctx.h)
+        return mu
+    x, code = _host_vec(psi0)
+    check(lib().sd_kpm_site_moments(model.ctx.h, model.h, code, x.ctypes.data, len(x), src.ctypes.data_as(_ip), len(src), int(M),
+                                    float(a), float(b), mu.ctypes.data_as(_dp)), model.ctx.h)
+    return mu
+
+
+def kpm_reconstruct_signed(mu_damped, omega, a, b, E0):
+    """kpm_reconstruct without the clamp at zero (off-diagonal C_ij is signed); complex moments: Re and Im separately."""
+    mu = np.ascontiguousarray(mu_damped)
+    if np.iscomplexobj(mu):
+        return kpm_reconstruct_signed(mu.real, omega, a, b, E0) + 1j * kpm_reconstruct_signed(mu.imag, omega, a, b, E0)
+    mu = np.ascontiguousarray(mu, dtype=np.float64)
+    om = np.ascontiguousarray(omega, dtype=np.float64)
+    out = np.empty(len(om))
+    check(lib().sd_kpm_reconstruct_signed(mu.ctypes.data_as(_dp), len(mu), om.ctypes.data_as(_dp), len(om), float(a), float(b),
+                                          float(E0), out.ctypes.data_as(_dp)))
+    return out
+
+
+def kpm_correlation_matrix(psi0, model, omega, sources=None, a=None, b=None, kpm_m=200, kernel="jackson", seed=0):
+    """C[i-1, s, w] = <psi0| S^z_i delta(omega_w - (H - E0)) S^z_j |psi0>, j = sources[s] (None: all sites) -> complex array
+    (L, len(sources), len(omega)).  Rescaling (estimated from `seed` when a, b are not given), kernel and E0 as kpm_sqw; the
+    spectrum is NOT clamped at zero.  The reference's kpm_correlation_matrix (src/TimeEvolution/KPM.jl) is the model, with its
+    defects left behind."""
+    x, code = _host_vec(psi0)
+    src = _sources(model, sources)
+    om = np.ascontiguousarray(omega, dtype=np.float64)
+    out = np.empty((model.L, len(src), len(om)), dtype=np.complex128)
+    have = a is not None and b is not None
+    check(lib().sd_kpm_site_correlations(model.ctx.h, model.h, code, x.ctypes.data, len(x), src.ctypes.data_as(_ip), len(src),
+                                         om.ctypes.data_as(_dp), len(om), int(have), float(a) if have else 0.0,
+                                         float(b) if have else 0.0, int(kpm_m), _lib.KERNELS.get(kernel, 2), int(seed),
+                                         out.ctypes.data_as(_dp)), model.ctx.h)
+    return out
+
+
+def _shift_invariant(model):
+    """Are the hop / zz / field lists of `model` invariant under the cyclic shift i -> i + 1 (mod L)?"""
+    L = model.L
+
+    def table(bonds):
+        t = {}
+        for i, j, J in bonds:
+            if i == j:
+                continue
+            key = (min(i, j), max(i, j))
+            t[key] = t.get(key, 0.0) + J
+        return {k: v for k, v in t.items() if v != 0.0}
+
+    def shifted(t):
+        return {(min(i % L + 1, j % L + 1), max(i % L + 1, j % L + 1)): v for (i, j), v in t.items()}
+
+    for bonds in (model.hopping_list, model.zz_list):
+        t = table(bonds)
+        if shifted(t) != t:
+            return False
+    f = np.asarray(model.onsite_field)
+    return bool(np.all(f == f[0])) if len(f) else True
+
+
+def kpm_sqw_sites(psi0, model, q_list, omega, a=None, b=None, kpm_m=200, kernel="jackson", seed=0,
+                  translation_invariant=False, source=1, ti_tol=1e-6):
+    """S^zz(q, omega) at every q of the list from the site-resolved moments -> Smat[Qn, W], the rows kpm_sqw returns.
+
+    translation_invariant=False: one recursion per site (L x (kpm_m - 1) applies) for any psi0, any boundary and any number
+    of momenta.  translation_invariant=True: ONE recursion from site `source` gives every momentum -- valid when H and psi0
+    are invariant under the cyclic shift (the ground state of a periodic chain).  The lists are checked first (ArgumentError
+    when the shift changes them), and the state through the invariance defect max |Im mu_n(q)| / (|psi0|^2 / 4) the library
+    returns: ArgumentError above ti_tol (an invariant state sits at 1e-14, a violating one at >= 0.1)."""
+    x, code = _host_vec(psi0)
+    q = np.ascontiguousarray(q_list, dtype=np.float64)
+    om = np.ascontiguousarray(omega, dtype=np.float64)
+    if translation_invariant:
+        if not _shift_invariant(model):
+            raise ArgumentError("translation_invariant=True needs hop / zz / field lists that the cyclic shift leaves unchanged "
+                                "(a periodic chain); use translation_invariant=False")
+        src = _sources(model, [source])
+    else:
+        src = _sources(model, None)
+    S = np.empty((len(q), len(om)))
+    have = a is not None and b is not None
+    defect = C.c_double(0.0)
+    check(lib().sd_kpm_sqw_sites(model.ctx.h, model.h, code, x.ctypes.data, len(x), q.ctypes.data_as(_dp), len(q),
+                                 om.ctypes.data_as(_dp), len(om), src.ctypes.data_as(_ip), len(src), int(bool(translation_invariant)),
+                                 int(have), float(a) if have else 0.0, float(b) if have else 0.0, int(kpm_m),
+                                 _lib.KERNELS.get(kernel, 2), int(seed), S.ctypes.data_as(_dp), C.byref(defect)), model.ctx.h)
+    kpm_sqw_sites.last_defect = defect.value
+    if translation_invariant and not defect.value <= ti_tol:
+        raise ArgumentError(f"psi0 is not translation invariant: defect {defect.value:.3e} > ti_tol {ti_tol:.1e}; "
+                            "use translation_invariant=False")
+    return S
+
+
+kpm_sqw_sites.last_defect = 0.0
+
+
 def symtridiag_eig(d, e, vectors=True):
     d = np.ascontiguousarray(d, dtype=np.float64)
     e = np.ascontiguousarray(e, dtype=np.float64)
