@@ -304,6 +304,69 @@ int sd_kpm_sqw_sites(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0
                      const double *omega, int W, const int *sources, int ns, int translation_invariant, int have_ab, double a,
                      double b, int kpm_m, int kernel, uint64_t seed, double *Smat_out, double *defect_out);
 
+/* ---- finite temperature by dynamical quantum typicality, with the spin current ----------------------------------------
+ * The quantity of the reference's src/TimeEvolution/QuantumTypicality.jl (typicality_correlation_function, :33-91), a module
+ * the reference never includes and that calls undefined names; built here on this library's own definitions:
+ *   psi_beta = exp(-beta H / 2) r for a start vector r;  num_r(t) = <psi_beta(t)| A |phi(t)>,  psi_beta(t) = exp(-iHt) psi_beta,
+ *   phi(t) = exp(-iHt) B psi_beta;  den_r = |psi_beta|^2;  <A(t) B>_beta ~ sum_r num_r(t) / sum_r den_r.
+ * Unlike the reference (:86-87, which leaves the bra at t = 0) the bra is evolved as well; the model is an argument (the
+ * reference hard-wires nup = L/2); operators are descriptors so that the loop stays on the device; no :rk4 method.
+ *
+ * Spin current.  With hops (i_b, j_b, t_b) the bond current is j_b = i t_b (S^+_{i_b} S^-_{j_b} - S^-_{i_b} S^+_{j_b}): Hermitian,
+ * carrying S^z from site i_b to site j_b, i[H, S^z_k] = sum_{b: j_b = k} j_b - sum_{b: i_b = k} j_b.  J_w = sum_b w_b j_b with real
+ * weights w (n_hop doubles; NULL: ones, the total current).  Row form, as computed:
+ *   (J_w psi)[s] = i * sum_{b: s_{i_b} != s_{j_b}} (w_b t_b sigma_b(s)) * psi[flip_b(s)],  sigma_b = +1 when site i_b is up in s,
+ * in hop-list order from a zero accumulator, no fused multiply-add, the factor i as the exact swap (re, im) -> (-im, re).
+ * Unsharded models only (SD_EARG otherwise). */
+#define SD_EVOLVE_CHEBYSHEV 0
+#define SD_EVOLVE_KRYLOV 1
+/* c_out[k] = (2 - delta_k0) (-1)^k exp(-z) I_k(z), z = a * tau, k = 0 .. *n_used - 1: exp(-z x) exp(-z) = sum_k c_k T_k(x) on
+ * [-1, 1].  *n_used is the first k with k > z and exp(-z) I_k(z) < 2^-53 exp(-z) I_0(z).  Scaled Bessel functions, nothing
+ * overflows.  SD_EARG when z < 0, z > 600 or *n_used > n_max (host only). */
+int sd_chebyshev_imag_coeffs(int n_max, double a, double tau, double *c_out, int *n_used);
+/* out = exp(-tau H) psi0 / |.| (ComplexF64, n elements), *log_norm = ln |exp(-tau H) psi0|; psi0 of `dtype`, tau >= 0.
+ * method SD_EVOLVE_CHEBYSHEV: exp(-tau H) = exp(-tau (b - a)) sum_k c_k T_k((H - b)/a) with the coefficients above and
+ *   a = (Emax - Emin)/(2 * 0.9999), b = (Emax + Emin)/2 through the term loop of sd_chebyshev_evolve; cheb_n = 0 takes *n_used
+ *   terms, cheb_n > 0 at most cheb_n; z = a * tau > 600 is split into equal sub-steps, the vector renormalised after each and the
+ *   logarithms added up.  Emax <= Emin: the bounds are estimated as sd_energy_bounds does, seed 0.
+ * method SD_EVOLVE_KRYLOV: krylov_imaginary_time_evolution (src/TimeEvolution/QuantumTypicality.jl:154-211) on the Lanczos vectors
+ *   of sd_krylov_evolve: exp(-tau theta) in place of the phase, ONE projection on kry_m vectors, no sub-stepping -- accurate
+ *   only while tau * (bandwidth) is small against kry_m.
+ * _dev: psi0_dev, out_dev device pointers (out_dev may be psi0_dev for a ComplexF64 psi0); the call synchronises the stream. */
+int sd_imag_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, double tau, int method,
+                   int cheb_n, int kry_m, double Emin, double Emax, void *out_c128_host, double *log_norm);
+int sd_imag_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, double tau, int method,
+                       int cheb_n, int kry_m, double Emin, double Emax, void *out_c128_dev, double *log_norm);
+/* out (ComplexF64, n elements) = J_w psi, psi of `dtype`.  _dev: device pointers, out_dev must not alias psi_dev. */
+int sd_current_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const double *w,
+                     void *out_c128_host);
+int sd_current_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const double *w,
+                         void *out_c128_dev);
+/* out[0..1] (host) = (re, im) of <bra| J_w |ket> WITHOUT writing J_w ket: one pass over bra (`dtype_bra`, not promoted) and ket
+ * (ComplexF64) plus the gathers, per-block sums reduced in a fixed order -- no atomics, the same call gives the same bits. */
+int sd_current_bracket(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_host, const void *ket_c128_host, int64_t n,
+                       const double *w, double *out);
+int sd_current_bracket_dev(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_dev, const void *ket_c128_dev, int64_t n,
+                           const double *w, double *out);
+/* operator kinds of sd_dqt_correlations; `param` is the site (1-based) or the momentum q, `w` the weights of a current */
+#define SD_DQT_SZ_SITE 0   /* S^z_site */
+#define SD_DQT_SZ_Q 1      /* S^z_q of sd_szq; as the measured operator A its adjoint: <S^z_q psi| phi> */
+#define SD_DQT_SZ_ALL 2    /* A only: S^z_i for every site i = 1..L at once (nA = L) */
+#define SD_DQT_CURRENT 3   /* J_w of the model's hop list (also with a caller's operator) */
+/* One sample of <A(t) B>_beta.  r_host: the start vector (ComplexF64, n = sd_model_dim elements) or NULL for the counter-based
+ * normal stream of `seed` (sd_fill_randn_host(x, 2n, seed, 0) gives the same vector on the host); it is normalised first.
+ * beta >= 0 (0 skips the imaginary-time step); times[nt] non-decreasing, times[0] >= 0.  method / cheb_n / kry_m / Emin / Emax as
+ * sd_imag_evolve (bounds estimated from `seed` when Emax <= Emin); real-time Chebyshev steps take the first k with k > a dt and
+ * |J_k(a dt)| < 2^-53 terms when cheb_n == 0, and equal steps share their coefficients.  The two states share their launches
+ * under the conditions of sd_ctx_set_q_batch (bit-identical to separate launches).  A caller's operator is honoured for the
+ * evolution.  Outputs (host): num_out[(k * nA + i) * 2 .. +1] = (re, im) of <psi(t_k)| A_i |phi(t_k)> for the NORMALISED
+ * psi_beta -- num_r(t_k) = *den_out * num_out --, *den_out = exp(2 * *log_norm) = |psi_beta|^2 (may overflow; *log_norm does not),
+ * *energy_out = <psi_beta|H|psi_beta> / <psi_beta|psi_beta>.  All measurements are filed on the device and read back once. */
+int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, const void *r_host, uint64_t seed, int B_kind,
+                        double B_param, const double *w_B, int A_kind, double A_param, const double *w_A, const double *times,
+                        int nt, int method, int cheb_n, int kry_m, double Emin, double Emax, double *num_out, double *den_out,
+                        double *energy_out, double *log_norm);
+
 /* ---- observables and initial states (reference src/Observables.jl, src/InitialStates.jl) ---- */
 /* magnetization_per_site   src/Observables.jl:14-36 : mags_out[L] = <S^z_i> */
 int sd_magnetization(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, double *mags_out);

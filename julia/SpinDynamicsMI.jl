@@ -21,6 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
+       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -440,6 +441,100 @@ function kpm_sqw_sites(ψ0::AbstractVector, model::Model, q::AbstractVector, ω:
         throw(ArgumentError("psi0 is not translation invariant: defect $(defect[]) > ti_tol $ti_tol"))
     end
     return permutedims(S)
+end
+
+# ---- finite temperature by dynamical quantum typicality, with the spin current (DESIGN.md 14) -------------------------------
+# The quantity of the reference's src/TimeEvolution/QuantumTypicality.jl (never included there, calls undefined names):
+# ψ_β = exp(-βH/2) r, num_r(t) = <ψ_β(t)| A |φ(t)>, φ(t) = exp(-iHt) B ψ_β, <A(t)B>_β ≈ Σ_r num_r(t) / Σ_r |ψ_β|².
+evolve_code(method::Symbol) = method === :chebyshev ? 0 : method === :krylov ? 1 :
+    throw(ArgumentError("unknown evolution method: $method"))
+
+# c_k = (2 - δ_k0) (-1)^k exp(-z) I_k(z), z = a τ; the first k with k > z and exp(-z) I_k(z) < 2^-53 exp(-z) I_0(z) terms
+function chebyshev_imag_coeffs(a::Real, τ::Real; n_max::Int=4096)
+    c = Vector{Float64}(undef, n_max)
+    n_used = Ref{Cint}(0)
+    check(ccall((:sd_chebyshev_imag_coeffs, libspindyn), Cint, (Cint, Float64, Float64, Ptr{Float64}, Ref{Cint}),
+                n_max, Float64(a), Float64(τ), c, n_used))
+    return c[1:n_used[]]
+end
+
+# (exp(-βH/2) r / |.|, ln |exp(-βH/2) r|)
+function thermal_state(model::Model, β::Real, r::AbstractVector; method::Symbol=:chebyshev, cheb_n::Int=0, kry_m::Int=30,
+                       Ebounds::Union{Nothing,Tuple{Float64,Float64}}=nothing)
+    x = Vector{ComplexF64}(r)
+    out = Vector{ComplexF64}(undef, length(x))
+    log_norm = Ref{Float64}(0.0)
+    lo, hi = Ebounds === nothing ? (0.0, 0.0) : Ebounds
+    check(ccall((:sd_imag_evolve, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Float64, Cint, Cint, Cint, Float64, Float64, Ptr{Cvoid}, Ref{Float64}),
+                model.ctx.h, model.h, dtype_code(ComplexF64), x, length(x), Float64(β) / 2, evolve_code(method), cheb_n, kry_m, lo, hi,
+                out, log_norm), model.ctx.h)
+    return out, log_norm[]
+end
+
+current_weights(model::Model, weights) = weights === nothing ? Ptr{Float64}(C_NULL) :
+    (length(weights) == length(model.hopping_list) ? Vector{Float64}(weights) :
+     throw(ArgumentError("weights must have one entry per hop")))
+
+# J_w ψ, J_w = Σ_b w_b i t_b (S⁺_i S⁻_j - S⁻_i S⁺_j) over the model's hop list (weights nothing: the total current)
+function spin_current(ψ::AbstractVector, model::Model; weights=nothing)
+    x = hostvec(ψ); w = current_weights(model, weights)
+    out = Vector{ComplexF64}(undef, length(x))
+    check(ccall((:sd_current_apply, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Cvoid}),
+                model.ctx.h, model.h, dtype_code(eltype(x)), x, length(x), w, out), model.ctx.h)
+    return out
+end
+
+# <bra| J_w |ket> without forming J_w ket
+function current_expectation(bra::AbstractVector, ket::AbstractVector, model::Model; weights=nothing)
+    b = hostvec(bra); k = Vector{ComplexF64}(ket); w = current_weights(model, weights)
+    length(b) == length(k) || throw(DimensionMismatch("length(bra) != length(ket)"))
+    out = Vector{Float64}(undef, 2)
+    check(ccall((:sd_current_bracket, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(b)), b, k, length(k), w, out), model.ctx.h)
+    return complex(out[1], out[2])
+end
+
+# operator descriptors: (:Sz, site), (:Szq, q), :Sz_all (operator_i only), (:current, weights | nothing) -> (kind, parameter, weights)
+function dqt_operator(model::Model, op)
+    op === :Sz_all && return (2, 0.0, Ptr{Float64}(C_NULL))
+    op isa Tuple && length(op) == 2 || throw(ArgumentError("unknown operator: $op"))
+    op[1] === :Sz && return (0, Float64(op[2]), Ptr{Float64}(C_NULL))
+    op[1] === :Szq && return (1, Float64(op[2]), Ptr{Float64}(C_NULL))
+    op[1] === :current && return (3, 0.0, current_weights(model, op[2]))
+    throw(ArgumentError("unknown operator: $op"))
+end
+
+# One sample: (num[i, k] for the normalised ψ_β, den = |ψ_β|², energy, log_norm); r nothing: the counter-based stream of `seed`.
+function typicality_sample(model::Model, β::Real, operator_i, operator_j, t_range::AbstractVector; method::Symbol=:chebyshev,
+                           r::Union{Nothing,AbstractVector}=nothing, seed::Integer=0, cheb_n::Int=0, kry_m::Int=30,
+                           Ebounds::Union{Nothing,Tuple{Float64,Float64}}=nothing)
+    Ak, Ap, Aw = dqt_operator(model, operator_i)
+    Bk, Bp, Bw = dqt_operator(model, operator_j)
+    Bk == 2 && throw(ArgumentError(":Sz_all is for operator_i only"))
+    times = Float64.(t_range)
+    nA = Ak == 2 ? model.L : 1
+    num = Matrix{ComplexF64}(undef, nA, length(times))
+    den = Ref{Float64}(0.0); energy = Ref{Float64}(0.0); log_norm = Ref{Float64}(0.0)
+    rr = r === nothing ? Ptr{Cvoid}(C_NULL) : Vector{ComplexF64}(r)
+    lo, hi = Ebounds === nothing ? (0.0, 0.0) : Ebounds
+    check(ccall((:sd_dqt_correlations, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, UInt64, Cint, Float64, Ptr{Float64}, Cint, Float64, Ptr{Float64},
+                 Ptr{Float64}, Cint, Cint, Cint, Cint, Float64, Float64, Ptr{Float64}, Ref{Float64}, Ref{Float64}, Ref{Float64}),
+                model.ctx.h, model.h, Float64(β), rr, seed, Bk, Bp, Bw, Ak, Ap, Aw, times, length(times), evolve_code(method), cheb_n,
+                kry_m, lo, hi, num, den, energy, log_norm), model.ctx.h)
+    return num, den[], energy[], log_norm[]
+end
+
+# <A(t)B>_β ≈ Σ_r num_r(t) / Σ_r den_r over n_samples start vectors (sample k: seed + k) -> (length(t_range),) or (L, length(t_range))
+function typicality_correlation_function(model::Model, β::Real, operator_i, operator_j, t_range::AbstractVector;
+                                         method::Symbol=:chebyshev, n_samples::Int=1, seed::Integer=0, kw...)
+    samples = [typicality_sample(model, β, operator_i, operator_j, t_range; method=method, seed=seed + k, kw...) for k in 0:n_samples-1]
+    shift = maximum(s[4] for s in samples)
+    wgt = [exp(2 * (s[4] - shift)) for s in samples]
+    C = sum(wgt[k] .* samples[k][1] for k in 1:n_samples) ./ sum(wgt)
+    return operator_i === :Sz_all ? C : vec(C)
 end
 
 end # module

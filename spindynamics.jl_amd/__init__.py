@@ -16,6 +16,8 @@ from .solvers import (chebyshev_coeffs, chebyshev_time_evolve, compute_chebyshev
                       krylov_time_evolve, lanczos_extremal, lanczos_groundstate, lanczos_sqw, lanczos_sqw_transverse,
                       lanczos_tridiag, rescaling_from_bounds, spectral_from_tridiagonal, symtridiag_eig,
                       kpm_correlation_matrix, kpm_reconstruct_signed, kpm_site_moments, kpm_sqw_sites, site_project)
+from .typicality import (chebyshev_imag_coeffs, current_expectation, dqt_sample, spin_current, thermal_energy, thermal_state,
+                         typicality_correlation_function)
 from .observables import connected_correlations, magnetization_per_site, structure_factor_Sq
 from . import initial_states
 from .initial_states import domain_wall_state, neel_state, polarized_state, polarized_state_with_flips

@@ -15,6 +15,7 @@ SD_OK, SD_EARG, SD_EDIM, SD_EZERO, SD_ENOMEM, SD_EHIP, SD_ENODEV, SD_EINTERNAL, 
 SD_F64, SD_C128 = 1, 2
 KERNELS = {"jackson": 0, "lorentz": 1}
 BROADEN = {"lorentz": 0, "gauss": 1}
+EVOLVE = {"chebyshev": 0, "krylov": 1}
 
 
 class SpinDynError(RuntimeError):
@@ -140,6 +141,14 @@ PROTOTYPES = {
     "sd_kpm_reconstruct_signed": (_i, [_dp, _i, _dp, _i, _d, _d, _d, _dp]),
     "sd_kpm_site_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _dp, _i, _i, _d, _d, _i, _i, _u64, _dp]),
     "sd_kpm_sqw_sites": (_i, [_vp, _vp, _i, _vp, _i64, _dp, _i, _dp, _i, _ip, _i, _i, _i, _d, _d, _i, _i, _u64, _dp, _dp]),
+    "sd_chebyshev_imag_coeffs": (_i, [_i, _d, _d, _dp, _ip]),
+    "sd_imag_evolve": (_i, [_vp, _vp, _i, _vp, _i64, _d, _i, _i, _i, _d, _d, _vp, _dp]),
+    "sd_imag_evolve_dev": (_i, [_vp, _vp, _i, _vp, _i64, _d, _i, _i, _i, _d, _d, _vp, _dp]),
+    "sd_current_apply": (_i, [_vp, _vp, _i, _vp, _i64, _dp, _vp]),
+    "sd_current_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _dp, _vp]),
+    "sd_current_bracket": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _dp, _dp]),
+    "sd_current_bracket_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _dp, _dp]),
+    "sd_dqt_correlations": (_i, [_vp, _vp, _d, _vp, _u64, _i, _d, _dp, _i, _d, _dp, _dp, _i, _i, _i, _i, _d, _d, _dp, _dp, _dp, _dp]),
     "sd_magnetization": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),
     "sd_magnetization_dev": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),
     "sd_connected_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),

@@ -163,6 +163,12 @@ int peek_breakdown(sd_ctx *ctx, const double *d_be, int count, double tol, std::
 // its per-tile pairs left unreduced, and one batched update pass that sums those pairs and the previous passes' |w|^2 pairs
 // itself (k_lanczos_fold_p).  Nothing touches the host until the end.  alpha, beta: Qb rows of mm (beta[., mm-1] unused).
 // Same arithmetic per element as the four-launch form; the reductions are summed in another (fixed) order.
+// May the vectors of independent recursions on `op` share their launches (sd_epi_args::batch)?  sd_ctx_set_q_batch is on, the
+// built-in operator on an unsharded tiled plan of at most 16384 tiles, vectors of at most 2^22 rows (launch-bound sizes).
+bool launches_shareable(const Op &op) {
+  const sd_model *m = op.m;
+  return op.ctx->q_batch && m->nranks == 1 && !op.ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 16384 && op.n <= ((int64_t)1 << 22);
+}
 bool lanczos_fused_ok(const Op &op, int Qb) {
   const sd_model *m = op.m;
   return m->nranks == 1 && !op.ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 4096 && op.n <= ((int64_t)1 << 22) &&
@@ -840,8 +846,13 @@ extern "C" int sd_lanczos_tridiag(sd_ctx *ctx, const sd_model *m, const void *v,
   return tridiag_dev(op, vc.p, lanc_m, tol, alpha, beta, m_eff);
 }); }
 
-// krylov_time_evolve; on_dev: psi0 / psit are device vectors (psit ComplexF64; may alias a ComplexF64 psi0)
-static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, double dt, int kry_m, void *psit, bool on_dev) {
+// krylov_time_evolve; on_dev: psi0 / psit are device vectors (psit ComplexF64; may alias a ComplexF64 psi0).
+// log_norm != null: the imaginary-time form (the reference's krylov_imaginary_time_evolution,
+// src/TimeEvolution/QuantumTypicality.jl:154-211) on the same Lanczos vectors -- exp(-dt theta_l) in place of the phase, one
+// projection; psit = exp(-dt H) psi0 / |.| and *log_norm = ln |exp(-dt H) psi0| (the reference returns the un-normalised vector;
+// the weights are formed as exp(-dt (theta_l - theta_min)) and dt theta_min goes into the logarithm, so nothing overflows).
+static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, double dt, int kry_m, void *psit, bool on_dev,
+                              double *log_norm = nullptr) {
   sd_ctx *ctx = op.ctx;
   if (!psi0 || !psit) return sd_set_err(ctx, SD_EARG, "null vector");
   auto emit = [&](const double *src) -> int {          // result to the caller
@@ -864,7 +875,10 @@ static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, do
   const double norm0 = norm_dev(op, inp, nc * n, &rc); RC(rc);
   RC(V[0].alloc(ctx, 2 * n));
   RC(sd_k_promote(ctx, V[0].p, inp, nc, n));
-  if (norm0 == 0) return emit(V[0].p);                                                    // :145-147
+  if (norm0 == 0) {                                                                       // :145-147
+    if (log_norm) return sd_set_err(ctx, SD_EZERO, "starting vector has zero norm");
+    return emit(V[0].p);
+  }
   RC(sd_k_scale_div(ctx, V[0].p, V[0].p, 2 * n, norm0));                                  // :148
   // the Lanczos part is queued without host round trips (see lanczos_coeffs): alpha_j (complex) and beta_j stay on the device
   // and are read back once; the break on |beta_j| < 1e-14 (:162-168) is applied to the values afterwards
@@ -925,7 +939,8 @@ static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, do
   if (sd_symtridiag_eig(m_eff, alr.data(), beta.data(), ev.data(), Q.data()))
     return sd_set_err(ctx, SD_EINTERNAL, "tridiagonal eigen-solver did not converge");
   for (int l = 0; l < m_eff; ++l) {
-    const double ph = -ev[l] * dt, cr = std::cos(ph), ci = std::sin(ph);
+    const double ph = -ev[l] * dt;
+    const double cr = log_norm ? std::exp(-(ev[l] - ev[0]) * dt) : std::cos(ph), ci = log_norm ? 0.0 : std::sin(ph);
     const double q0 = Q[(size_t)m_eff * l] * norm0;
     for (int k = 0; k < m_eff; ++k) {
       const double qk = Q[k + (size_t)m_eff * l];
@@ -939,6 +954,10 @@ static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, do
     RC(sd_k_ccombine(ctx, w.p, cols.data(), n, m_eff, yr.data(), yi.data()));
   }
   const double nn = norm_dev(op, w.p, 2 * n, &rc); RC(rc);
+  if (log_norm) {
+    if (!(nn > 0)) return sd_set_err(ctx, SD_EZERO, "the imaginary-time state has zero norm");
+    *log_norm = std::log(nn) - ev[0] * dt;
+  }
   RC(sd_k_scale_div(ctx, w.p, w.p, 2 * n, nn));                                           // :190
   return emit(w.p);
 }
@@ -961,6 +980,45 @@ extern "C" int sd_krylov_evolve_sharded(sd_ctx *ctx, const sd_model *m, sd_comm 
   return krylov_evolve_core(op, dtype, psi0_dev, n_local, dt, kry_m, psit_dev, true);
 }); }
 
+// The Chebyshev term loop (src/TimeEvolution/Chebyshev.jl:93-121) for a coefficient array: pt = sum_{k < cheb_n} c_k T_k(H~) phi_0
+// with H~ = (H - b)/a and c = cheb_n (re, im) pairs.  pprev holds phi_0 and is consumed, pcur / pnext are work vectors, pt must be
+// none of them.  batch > 1: `batch` vectors stored n elements apart in every buffer share the launches (sd_epi_args::batch; the
+// caller has checked that the plan allows it) -- each sees the arithmetic of a loop of its own.
+static int cheb_terms(Op &op, double *pprev, double *pcur, double *pnext, double *pt, int64_t n, double a, double b, const double *c,
+                      int cheb_n, int batch) {
+  sd_ctx *ctx = op.ctx;
+  sd_epi_args ea; ea.a = a; ea.b = b;
+  if (batch > 1) { ea.batch = batch; ea.bstride = n; }
+  const int64_t nb = n * batch;                     // the elementwise start runs over the whole batch at once
+  ctx->n_applies += batch - 1;                      // (Op::apply counts one)
+  RC(op.apply(SD_C128, pcur, pprev, SD_EPI_RESCALE, ea));                                 // :93
+  RC(sd_k_cheb_init(ctx, pt, pprev, pcur, nb, c[0], c[1], cheb_n >= 2 ? c[2] : 0.0, cheb_n >= 2 ? c[3] : 0.0,
+                    cheb_n >= 2));                                                        // :96-102
+  // :110-121, one fused pass per term.  Terms are taken in pairs: the first of a pair only advances the recurrence, the
+  // second adds both terms to psi_t in order (c_k phi_k is exact in the apply's input vector), so psi_t is read and
+  // written once per two terms -- same bits as one accumulation per term, 72 instead of 80 B/row per term.
+  int k = 2;
+  ea.accv = pt;
+  if ((cheb_n - 2) % 2 == 1) {
+    ea.prev = pprev; ea.c_re = c[2 * k]; ea.c_im = c[2 * k + 1];
+    ctx->n_applies += batch - 1;
+    RC(op.apply(SD_C128, pnext, pcur, SD_EPI_CHEB, ea));
+    double *t = pprev; pprev = pcur; pcur = pnext; pnext = t;
+    ++k;
+  }
+  for (; k + 1 <= cheb_n - 1; k += 2) {
+    ea.prev = pprev;
+    ctx->n_applies += batch - 1;
+    RC(op.apply(SD_C128, pnext, pcur, SD_EPI_RECUR, ea));                                 // phi_k
+    { double *t = pprev; pprev = pcur; pcur = pnext; pnext = t; }
+    ea.prev = pprev; ea.c0_re = c[2 * k]; ea.c0_im = c[2 * k + 1]; ea.c_re = c[2 * k + 2]; ea.c_im = c[2 * k + 3];
+    ctx->n_applies += batch - 1;
+    RC(op.apply(SD_C128, pnext, pcur, SD_EPI_CHEB2, ea));                                 // phi_{k+1}; psi_t += c_k phi_k + c_{k+1} phi_{k+1}
+    { double *t = pprev; pprev = pcur; pcur = pnext; pnext = t; }
+  }
+  return SD_OK;
+}
+
 // chebyshev_time_evolve on device vectors: psi0_dev (c128, n elements) is read, psit_dev receives psi(t); they may be the
 // same buffer (psi0 is copied into the recursion's own vectors first).  host_in / host_out select the host-pointer form.
 static int chebyshev_evolve_core(Op &op, const void *psi0, bool host_in, int64_t n, double dt, int cheb_n,
@@ -979,29 +1037,7 @@ static int chebyshev_evolve_core(Op &op, const void *psi0, bool host_in, int64_t
   else RC(d2d(ctx, pprev, (const double *)psi0, 2 * n));
   double *pt = (double *)psit;                    // psi_t accumulates in the caller's device buffer when there is one
   if (host_out) { RC(ptb.alloc(ctx, 2 * n)); pt = ptb.p; }
-  sd_epi_args ea; ea.a = a; ea.b = b;
-  RC(op.apply(SD_C128, pcur, pprev, SD_EPI_RESCALE, ea));                                 // :93
-  RC(sd_k_cheb_init(ctx, pt, pprev, pcur, n, c[0], c[1], cheb_n >= 2 ? c[2] : 0.0, cheb_n >= 2 ? c[3] : 0.0,
-                    cheb_n >= 2));                                                        // :96-102
-  // :110-121, one fused pass per term.  Terms are taken in pairs: the first of a pair only advances the recurrence, the
-  // second adds both terms to psi_t in order (c_k phi_k is exact in the apply's input vector), so psi_t is read and
-  // written once per two terms -- same bits as one accumulation per term, 72 instead of 80 B/row per term.
-  int k = 2;
-  ea.accv = pt;
-  if ((cheb_n - 2) % 2 == 1) {
-    ea.prev = pprev; ea.c_re = c[2 * k]; ea.c_im = c[2 * k + 1];
-    RC(op.apply(SD_C128, pnext, pcur, SD_EPI_CHEB, ea));
-    double *t = pprev; pprev = pcur; pcur = pnext; pnext = t;
-    ++k;
-  }
-  for (; k + 1 <= cheb_n - 1; k += 2) {
-    ea.prev = pprev;
-    RC(op.apply(SD_C128, pnext, pcur, SD_EPI_RECUR, ea));                                 // phi_k
-    { double *t = pprev; pprev = pcur; pcur = pnext; pnext = t; }
-    ea.prev = pprev; ea.c0_re = c[2 * k]; ea.c0_im = c[2 * k + 1]; ea.c_re = c[2 * k + 2]; ea.c_im = c[2 * k + 3];
-    RC(op.apply(SD_C128, pnext, pcur, SD_EPI_CHEB2, ea));                                 // phi_{k+1}; psi_t += c_k phi_k + c_{k+1} phi_{k+1}
-    { double *t = pprev; pprev = pcur; pcur = pnext; pnext = t; }
-  }
+  RC(cheb_terms(op, pprev, pcur, pnext, pt, n, a, b, c.data(), cheb_n, 1));
   if (host_out) RC(d2h(ctx, psit, pt, 2 * n));
   else SD_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the work vectors go back to the pool: nothing may still use them
   return SD_OK;
@@ -1117,9 +1153,7 @@ struct KpmSpectrum : Spectrum {
   // Launch-bound sizes: the momenta's vectors share their launches (moments_dev_batched): five batches of vectors (phi + the
   // recursion's three + nothing else) within 4 GiB, vectors of at most 2^22 rows.  sd_ctx_set_q_batch(ctx, 0): one momentum at a time.
   bool can_batch(int Qb) const override {
-    const sd_model *m = op.m;
-    return batchable && op.ctx->q_batch && Qb >= 2 && m->nranks == 1 && !op.ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 16384 &&
-           op.n <= ((int64_t)1 << 22) && (int64_t)Qb * op.n * 16 * 4 <= ((int64_t)4 << 30);
+    return batchable && Qb >= 2 && launches_shareable(op) && (int64_t)Qb * op.n * 16 * 4 <= ((int64_t)4 << 30);
   }
   void row(double *muk, double norm_phi, double *Srow) const {
     for (int k = 0; k < kpm_m; ++k) muk[k] *= g[k];                                         // :53
@@ -1331,7 +1365,7 @@ int site_moments_dev(Op &op, int dtype, const double *psi0, const int *sources, 
   if (!(a > 0.0) || !std::isfinite(a) || !std::isfinite(b)) return sd_set_err(ctx, SD_EARG, "the rescaling needs a finite a > 0 and a finite b");
   if (!psi0 || !mu) return sd_set_err(ctx, SD_EARG, "null argument");
   int Qmax = 1;
-  if (ctx->q_batch && ns >= 2 && !ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 16384 && N <= ((int64_t)1 << 22))
+  if (ns >= 2 && launches_shareable(op))
     Qmax = (int)std::min<int64_t>(ns, std::max<int64_t>(1, ((int64_t)4 << 30) / (std::max<int64_t>(N, 1) * 16 * 4)));
   const int64_t slot = 2 * (int64_t)L + 2, srow = slot * M;
   DBuf psic, b0, b1, b2, res;
@@ -1602,5 +1636,337 @@ extern "C" int sd_kpm_sqw_sites(sd_ctx *ctx, const sd_model *m, int dtype, const
     sd_kpm_reconstruct(muq.data(), M, omega, W, sp.a, sp.b, sp.E0, Smat + (size_t)iq * W);
   }
   if (defect_out) *defect_out = defect;
+  return SD_OK;
+}); }
+
+// --------------------------------------------------------------------------
+// Finite temperature by dynamical quantum typicality; the reference's unreachable module
+// src/TimeEvolution/QuantumTypicality.jl is the model, on this library's own definitions.
+// --------------------------------------------------------------------------
+namespace {
+
+// e_k = exp(-z) I_k(z), k = 0 .. n_used - 1, and n_used = the first k with k > z and e_k < 2^-53 e_0.  Ratios r_k = I_k / I_{k-1}
+// from the continued fraction r_k = 1 / (2k/z + r_{k+1}) started far above the last term kept, products t_k = r_1 ... r_k and the
+// normalisation exp(z) = I_0 + 2 sum_k I_k: all terms positive, no cancellation, no overflow at any z.  Extended precision on
+// the host, so that the rounded values are the correctly scaled Bessel functions to an ulp.
+void scaled_bessel_i(double z, std::vector<double> &e, int *n_used) {
+  if (z == 0.0) { e.assign(1, 1.0); *n_used = 1; return; }
+  const int ktop = (int)std::ceil(z) + 128;
+  std::vector<long double> t((size_t)ktop + 2);
+  long double r = 0.0L;
+  for (int k = ktop; k >= 1; --k) { r = 1.0L / (2.0L * (long double)k / (long double)z + r); t[k] = r; }
+  t[0] = 1.0L;
+  for (int k = 1; k <= ktop; ++k) t[k] *= t[k - 1];
+  long double S = 0.0L;
+  for (int k = ktop; k >= 1; --k) S += t[k];
+  S = 2.0L * S + t[0];
+  const double e0 = (double)(t[0] / S);
+  int nu = ktop;
+  for (int k = 1; k <= ktop; ++k)
+    if ((double)k > z && (double)(t[k] / S) < 0x1p-53 * e0) { nu = k; break; }
+  e.resize(nu);
+  for (int k = 0; k < nu; ++k) e[k] = (double)(t[k] / S);
+  *n_used = nu;
+}
+
+// real-time term count: the first k with k > z and |J_k(z)| < 2^-53, z = a dt
+// (the caller has checked 0 <= z <= SD_CHEB_ZMAX; the search is capped at k = z + 64 + 8 z^(1/3), well inside the Airy tail of J_k(z))
+constexpr double SD_CHEB_ZMAX = 1e6;
+int cheb_auto_terms(double z) {
+  int k = (int)std::floor(z) + 1;
+  const int kmax = (int)(z + 64.0 + 8.0 * std::cbrt(z));
+  while (k < kmax && !(std::fabs(std::cyl_bessel_j((double)k, z)) < 0x1p-53)) ++k;
+  return std::max(k, 1);
+}
+
+// Emin, Emax as given, or (Emax <= Emin) estimated as estimate_energy_bounds does; a spectrum of one point (a one-state sector)
+// gets half a unit on either side so that the rescaling H~ = (H - b)/a exists
+int typicality_bounds(Op &op, uint64_t seed, double *Emin, double *Emax) {
+  if (!std::isfinite(*Emin) || !std::isfinite(*Emax)) return sd_set_err(op.ctx, SD_EARG, "the energy bounds must be finite");
+  if (*Emax > *Emin) return SD_OK;
+  RC(energy_bounds_core(op, 80, nullptr, nullptr, true, seed, Emin, Emax));
+  if (!(*Emax - *Emin > 1e-8 * std::max(1.0, std::max(std::fabs(*Emin), std::fabs(*Emax))))) { *Emin -= 0.5; *Emax += 0.5; }
+  return SD_OK;
+}
+
+constexpr double SD_IMAG_ZMAX = 600.0;
+
+// v (device, ComplexF64, n elements) <- exp(-tau H) v / |.|, *log_norm = ln |exp(-tau H) v|.  Chebyshev: with H = a H~ + b,
+// exp(-tau H) = exp(-tau (b - a)) sum_k c_k T_k(H~), c_k = (2 - delta_k0) (-1)^k exp(-z) I_k(z), z = a tau, through the term loop
+// of chebyshev_time_evolve; z > 600 is split into equal sub-steps, renormalised after each, the logarithms added up.
+int imag_evolve_dev(Op &op, double *v, int64_t n, double tau, int method, int cheb_n, int kry_m, double Emin, double Emax,
+                    uint64_t seed, double *log_norm) {
+  sd_ctx *ctx = op.ctx;
+  if (!(tau >= 0.0) || !std::isfinite(tau)) return sd_set_err(ctx, SD_EARG, "the imaginary time must be finite and >= 0");
+  if (cheb_n < 0) return sd_set_err(ctx, SD_EARG, "cheb_n must be >= 0 (0: automatic)");
+  int rc = 0;
+  if (method == SD_EVOLVE_KRYLOV) return krylov_evolve_core(op, SD_C128, v, n, tau, kry_m, v, true, log_norm);
+  if (method != SD_EVOLVE_CHEBYSHEV) return sd_set_err(ctx, SD_EARG, "unknown evolution method");
+  RC(typicality_bounds(op, seed, &Emin, &Emax));
+  const double a = (Emax - Emin) / (2 * 0.9999), b = (Emax + Emin) / 2;
+  const double z = a * tau;
+  if (!(z <= SD_CHEB_ZMAX * SD_IMAG_ZMAX)) return sd_set_err(ctx, SD_EARG, "a * tau is too large: more than 1e6 sub-steps of z = 600");
+  const int nsub = z > SD_IMAG_ZMAX ? (int)std::ceil(z / SD_IMAG_ZMAX) : 1;
+  const double tsub = tau / nsub;
+  std::vector<double> e;
+  int nu = 0;
+  scaled_bessel_i(a * tsub, e, &nu);
+  const int nterm = cheb_n > 0 ? std::min(cheb_n, nu) : nu;
+  std::vector<double> c(2 * (size_t)nterm, 0.0);
+  for (int k = 0; k < nterm; ++k) c[2 * k] = (k == 0 ? 1.0 : 2.0) * ((k & 1) ? -e[k] : e[k]);
+  DBuf b0, b1, b2;
+  RC(b0.alloc(ctx, 2 * n)); RC(b1.alloc(ctx, 2 * n)); RC(b2.alloc(ctx, 2 * n));
+  double ln = 0.0;
+  for (int s = 0; s < nsub; ++s) {
+    RC(d2d(ctx, b0.p, v, 2 * n));
+    RC(cheb_terms(op, b0.p, b1.p, b2.p, v, n, a, b, c.data(), nterm, 1));
+    const double nn = norm_dev(op, v, 2 * n, &rc); RC(rc);
+    if (!(nn > 0) || !std::isfinite(nn)) return sd_set_err(ctx, SD_EZERO, "the imaginary-time state has zero or non-finite norm");
+    RC(sd_k_scale_div(ctx, v, v, 2 * n, nn));
+    ln += std::log(nn) - tsub * (b - a);
+  }
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *log_norm = ln;
+  return SD_OK;
+}
+
+int imag_evolve_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, double tau, int method, int cheb_n,
+                     int kry_m, double Emin, double Emax, void *out, double *log_norm, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (n != op.n) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!out || !log_norm) return sd_set_err(ctx, SD_EARG, "null argument");
+  DBuf in, vb;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi0, on_dev, n, in, &p));
+  double *v = (double *)out;
+  if (!on_dev) { RC(vb.alloc(ctx, 2 * n)); v = vb.p; }
+  if (dtype == SD_C128 && p == v) { /* in place */ }
+  else RC(sd_k_promote(ctx, v, p, dtype == SD_C128 ? 2 : 1, n));
+  if (tau == 0.0) {
+    int rc = 0;
+    const double nn = norm_dev(op, v, 2 * n, &rc); RC(rc);
+    if (!(nn > 0)) return sd_set_err(ctx, SD_EZERO, "starting vector has zero norm");
+    RC(sd_k_scale_div(ctx, v, v, 2 * n, nn));
+    *log_norm = std::log(nn);
+  } else {
+    RC(imag_evolve_dev(op, v, n, tau, method, cheb_n, kry_m, Emin, Emax, 0, log_norm));
+  }
+  if (!on_dev) return d2h(ctx, out, v, 2 * n);
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+
+// the n_hop products w_b t_b on the device (w == null: ones)
+int current_weights(sd_ctx *ctx, const sd_model *m, const double *w, DBuf &wt) {
+  const size_t nh = m->hop_J.size();
+  std::vector<double> h(std::max<size_t>(nh, 1), 0.0);
+  for (size_t b = 0; b < nh; ++b) {
+    if (w && !std::isfinite(w[b])) return sd_set_err(ctx, SD_EARG, "current weights must be finite");
+    h[b] = w ? w[b] * m->hop_J[b] : m->hop_J[b];
+  }
+  RC(wt.alloc(ctx, (int64_t)h.size()));
+  return h2d(ctx, wt.p, h.data(), (int64_t)h.size());
+}
+
+// write form (bra == null): out (ComplexF64, n) = J_w vec; bracket form: out[0..1] (host) = <bra|J_w|vec>, vec ComplexF64
+int current_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, bool bracket, int64_t n, const double *w,
+                 void *out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!out) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (!bracket && on_dev && out == vec) return sd_set_err(ctx, SD_EARG, "out must not alias psi");
+  DBuf wt, vin, bin, res;
+  const double *v = nullptr, *b = nullptr;
+  RC(current_weights(ctx, m, w, wt));
+  RC(site_stage(ctx, bracket ? SD_C128 : dtype, vec, on_dev, n, vin, &v));
+  if (bracket) {
+    RC(site_stage(ctx, dtype, bra, on_dev, n, bin, &b));
+    RC(res.alloc(ctx, 2));
+    RC(sd_launch_current(ctx, m, dtype, v, b, wt.p, nullptr, res.p));
+    SD_HIP(ctx, hipMemcpyAsync(out, res.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SD_OK;
+  }
+  double *o = (double *)out;
+  if (!on_dev) { RC(res.alloc(ctx, 2 * n)); o = res.p; }
+  RC(sd_launch_current(ctx, m, dtype, v, nullptr, wt.p, o, nullptr));
+  if (!on_dev) return d2h(ctx, out, o, 2 * n);
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));        // the weights go back to the pool
+  return SD_OK;
+}
+
+// an operator of the typicality driver: kind, site or momentum, device weights of a current
+struct DqtOp {
+  int kind = 0; int site = 0; double q = 0.0; DBuf wt;
+  int init(sd_ctx *ctx, const sd_model *m, int kind_, double param, const double *w, bool is_A) {
+    kind = kind_;
+    if (kind == SD_DQT_SZ_SITE) {
+      site = (int)param;
+      if ((double)site != param || site < 1 || site > m->L) return sd_set_err(ctx, SD_EARG, "site is outside 1..L");
+    } else if (kind == SD_DQT_SZ_Q) {
+      q = param;
+      if (!std::isfinite(q)) return sd_set_err(ctx, SD_EARG, "the momentum must be finite");
+    } else if (kind == SD_DQT_CURRENT) {
+      RC(current_weights(ctx, m, w, wt));
+    } else if (!(kind == SD_DQT_SZ_ALL && is_A)) {
+      return sd_set_err(ctx, SD_EARG, is_A ? "unknown operator kind" : "unknown operator kind (SD_DQT_SZ_ALL is for the measured operator only)");
+    }
+    return SD_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" int sd_chebyshev_imag_coeffs(int n_max, double a, double tau, double *c, int *n_used) {
+  if (!c || !n_used || n_max < 1) return SD_EARG;
+  const double z = a * tau;
+  if (!(z >= 0.0) || z > SD_IMAG_ZMAX) return SD_EARG;
+  try {
+    std::vector<double> e;
+    scaled_bessel_i(z, e, n_used);
+    if (*n_used > n_max) return SD_EARG;
+    for (int k = 0; k < *n_used; ++k) c[k] = (k == 0 ? 1.0 : 2.0) * ((k & 1) ? -e[k] : e[k]);
+  } catch (...) { return SD_ENOMEM; }
+  return SD_OK;
+}
+
+extern "C" int sd_imag_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, double tau, int method,
+                              int cheb_n, int kry_m, double Emin, double Emax, void *out_host, double *log_norm) {
+  return abi_guard(ctx, [&]() -> int { return imag_evolve_core(ctx, m, dtype, psi0_host, n, tau, method, cheb_n, kry_m, Emin, Emax, out_host, log_norm, false); });
+}
+extern "C" int sd_imag_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, double tau, int method,
+                                  int cheb_n, int kry_m, double Emin, double Emax, void *out_dev, double *log_norm) {
+  return abi_guard(ctx, [&]() -> int { return imag_evolve_core(ctx, m, dtype, psi0_dev, n, tau, method, cheb_n, kry_m, Emin, Emax, out_dev, log_norm, true); });
+}
+
+extern "C" int sd_current_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const double *w,
+                                void *out_host) {
+  return abi_guard(ctx, [&]() -> int { return current_core(ctx, m, dtype, psi_host, nullptr, false, n, w, out_host, false); });
+}
+extern "C" int sd_current_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const double *w,
+                                    void *out_dev) {
+  return abi_guard(ctx, [&]() -> int { return current_core(ctx, m, dtype, psi_dev, nullptr, false, n, w, out_dev, true); });
+}
+extern "C" int sd_current_bracket(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_host, const void *ket_host, int64_t n,
+                                  const double *w, double *out) {
+  return abi_guard(ctx, [&]() -> int {
+    if (!bra_host) return sd_set_err(ctx, SD_EARG, "null argument");
+    return current_core(ctx, m, dtype_bra, ket_host, bra_host, true, n, w, out, false);
+  });
+}
+extern "C" int sd_current_bracket_dev(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_dev, const void *ket_dev, int64_t n,
+                                      const double *w, double *out) {
+  return abi_guard(ctx, [&]() -> int {
+    if (!bra_dev) return sd_set_err(ctx, SD_EARG, "null argument");
+    return current_core(ctx, m, dtype_bra, ket_dev, bra_dev, true, n, w, out, true);
+  });
+}
+
+extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, const void *r_host, uint64_t seed, int B_kind,
+                                   double B_param, const double *w_B, int A_kind, double A_param, const double *w_A,
+                                   const double *times, int nt, int method, int cheb_n, int kry_m, double Emin, double Emax,
+                                   double *num, double *den, double *energy, double *log_norm) { return abi_guard(ctx, [&]() -> int {
+  Op op; RC(op.init(ctx, m, nullptr));
+  const int64_t n = op.n;
+  const int L = m->L;
+  if (!times || nt < 1 || !num || !den || !energy || !log_norm) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (!(beta >= 0.0) || !std::isfinite(beta)) return sd_set_err(ctx, SD_EARG, "beta must be finite and >= 0");
+  if (!(times[0] >= 0.0)) return sd_set_err(ctx, SD_EARG, "times must start at t >= 0");
+  for (int k = 0; k < nt; ++k)
+    if (!std::isfinite(times[k]) || (k > 0 && times[k] < times[k - 1])) return sd_set_err(ctx, SD_EARG, "times must be finite and non-decreasing");
+  if (method != SD_EVOLVE_CHEBYSHEV && method != SD_EVOLVE_KRYLOV) return sd_set_err(ctx, SD_EARG, "unknown evolution method");
+  if (cheb_n < 0) return sd_set_err(ctx, SD_EARG, "cheb_n must be >= 0 (0: automatic)");
+  if (method == SD_EVOLVE_KRYLOV && kry_m < 1) return sd_set_err(ctx, SD_EARG, "kry_m must be >= 1");
+  DqtOp Bo, Ao;
+  RC(Bo.init(ctx, m, B_kind, B_param, w_B, false));
+  RC(Ao.init(ctx, m, A_kind, A_param, w_A, true));
+  const int nA = A_kind == SD_DQT_SZ_ALL ? L : 1;
+  const int64_t mrow = A_kind == SD_DQT_SZ_ALL ? 2 * (int64_t)L + 2 : 2;      // doubles filed per time point
+  // the two states live back to back -- psi_beta at [0, n), phi = B psi_beta at [n, 2n) -- so that one batched launch serves both
+  DBuf s0, s1, w0, w1, tmp, meas;
+  RC(s0.alloc(ctx, 4 * n)); RC(tmp.alloc(ctx, 2 * n)); RC(meas.alloc(ctx, mrow * nt));
+  double *S = s0.p;
+  int rc = 0;
+  // 1. the start vector: the caller's, or the counter-based normal stream of `seed` (sd_fill_randn_host gives the same on the host)
+  if (r_host) RC(h2d(ctx, S, r_host, 2 * n));
+  else RC(sd_k_fill_randn(ctx, S, 2 * n, seed, 0));
+  const double nr = norm_dev(op, S, 2 * n, &rc); RC(rc);
+  if (!(nr > 0) || !std::isfinite(nr)) return sd_set_err(ctx, SD_EZERO, "starting vector has zero norm");
+  RC(sd_k_scale_div(ctx, S, S, 2 * n, nr));
+  // 2. psi_beta = exp(-beta H / 2) r, normalised; the sample's partition weight is exp(2 log_norm)
+  if (method == SD_EVOLVE_CHEBYSHEV) RC(typicality_bounds(op, seed, &Emin, &Emax));
+  double ln = 0.0;
+  if (beta > 0.0) RC(imag_evolve_dev(op, S, n, 0.5 * beta, method, cheb_n, kry_m, Emin, Emax, seed, &ln));
+  *log_norm = ln;
+  *den = std::exp(2.0 * ln);
+  // 3. energy = <psi|H|psi> / <psi|psi>
+  {
+    sd_epi_args ea;
+    double s[4];
+    RC(op.apply(SD_C128, tmp.p, S, SD_EPI_DOT, ea));
+    RC(sd_k_nrm2sq(ctx, S, 2 * n, 2));
+    RC(sd_read_scalars(ctx, 0, 4, s));
+    *energy = s[0] / s[2];
+  }
+  // 4. phi = B psi_beta
+  double *phi = S + 2 * n;
+  if (B_kind == SD_DQT_SZ_SITE) RC(sd_launch_spin_op(ctx, m, SD_C128, Bo.site, SD_SPIN_Z, S, phi));
+  else if (B_kind == SD_DQT_SZ_Q) RC(sd_launch_szq(ctx, m, SD_C128, S, Bo.q, phi));
+  else RC(sd_launch_current(ctx, m, SD_C128, S, nullptr, Bo.wt.p, phi, nullptr));
+  double nphi = 0.0;
+  if (method == SD_EVOLVE_KRYLOV) { nphi = norm_dev(op, phi, 2 * n, &rc); RC(rc); }
+  // 5. both states forward in time, a measurement after every step, everything filed on the device
+  const bool batched = launches_shareable(op);               // two vectors of at most 2^22 rows: well inside the 4 GiB of can_batch
+  const double a = (Emax - Emin) / (2 * 0.9999), b = (Emax + Emin) / 2;
+  double *T = nullptr;
+  if (method == SD_EVOLVE_CHEBYSHEV && times[nt - 1] > 0.0) {
+    RC(s1.alloc(ctx, 4 * n)); RC(w0.alloc(ctx, 4 * n)); RC(w1.alloc(ctx, 4 * n));
+    T = s1.p;
+  }
+  std::vector<double> c;
+  double c_dt = -1.0, t_prev = 0.0;
+  int nterm = 0;
+  for (int k = 0; k < nt; ++k) {
+    const double dt = times[k] - t_prev;
+    t_prev = times[k];
+    if (dt > 0.0 && method == SD_EVOLVE_CHEBYSHEV) {
+      if (dt != c_dt) {                                      // equal steps reuse their coefficients
+        if (!(a * dt <= SD_CHEB_ZMAX)) return sd_set_err(ctx, SD_EARG, "a * dt is too large for one Chebyshev step (above 1e6): give more time points");
+        nterm = cheb_n > 0 ? cheb_n : cheb_auto_terms(a * dt);
+        c.resize(2 * (size_t)nterm);
+        sd_chebyshev_coeffs(nterm, a, b, dt, c.data());
+        c_dt = dt;
+      }
+      if (batched) {
+        RC(cheb_terms(op, S, w0.p, w1.p, T, n, a, b, c.data(), nterm, 2));
+      } else {
+        for (int v = 0; v < 2; ++v) RC(cheb_terms(op, S + 2 * n * v, w0.p + 2 * n * v, w1.p + 2 * n * v, T + 2 * n * v, n, a, b, c.data(), nterm, 1));
+      }
+      std::swap(S, T);
+    } else if (dt > 0.0) {
+      // krylov_time_evolve normalises its result; a unitary step conserves the norm, so phi gets its own back
+      RC(krylov_evolve_core(op, SD_C128, S, n, dt, kry_m, S, true));
+      RC(krylov_evolve_core(op, SD_C128, S + 2 * n, n, dt, kry_m, S + 2 * n, true));
+      if (nphi > 0.0) RC(sd_k_scale_div(ctx, S + 2 * n, S + 2 * n, 2 * n, 1.0 / nphi));
+    }
+    const double *psi = S, *ph = S + 2 * n;
+    double *dst = meas.p + mrow * k;
+    if (A_kind == SD_DQT_SZ_SITE) {
+      RC(sd_launch_spin_op(ctx, m, SD_C128, Ao.site, SD_SPIN_Z, psi, tmp.p));
+      RC(sd_k_dot_to(ctx, 2, tmp.p, ph, n, dst));
+    } else if (A_kind == SD_DQT_SZ_Q) {                      // the adjoint: <S^z_q psi | phi>
+      RC(sd_launch_szq(ctx, m, SD_C128, psi, Ao.q, tmp.p));
+      RC(sd_k_dot_to(ctx, 2, tmp.p, ph, n, dst));
+    } else if (A_kind == SD_DQT_SZ_ALL) {
+      RC(sd_launch_site_project(ctx, m, SD_C128, psi, 0, ph, n, 1, dst, mrow));
+    } else {
+      RC(sd_launch_current(ctx, m, SD_C128, ph, psi, Ao.wt.p, nullptr, dst));
+    }
+  }
+  std::vector<double> h((size_t)(mrow * nt));
+  SD_HIP(ctx, hipMemcpyAsync(h.data(), meas.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < nt; ++k)
+    std::memcpy(num + (size_t)2 * nA * k, h.data() + (size_t)mrow * k, sizeof(double) * 2 * (size_t)nA);
   return SD_OK;
 }); }

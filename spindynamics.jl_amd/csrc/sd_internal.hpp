@@ -281,6 +281,12 @@ int sd_launch_spm_q(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int o
 int sd_launch_site_project(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra, int64_t bra_bstride, const void *ket,
                            int64_t bstride, int batch, double *dst, int64_t dstride);
 
+// Spin current J_w = sum_b w_b i t_b (S^+_i S^-_j - S^-_i S^+_j) of the hop list (kernels_current.hip).  out != null: out (ComplexF64)
+// = J_w vec, vec of `dtype`; out == null: dst[0..1] (device) = <bra|J_w|vec> with bra of `dtype` and vec ComplexF64, nothing
+// written.  wt_dev: the n_hop products w_b t_b on the device.  Unsharded models; queued on the context's stream, deterministic.
+int sd_launch_current(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, const double *wt_dev, void *out,
+                      double *dst);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.
