@@ -9,54 +9,12 @@ partner index by ranking the flipped configuration, psi at the partner rows gath
 list order.  Nothing of the library takes part in the expected values except the random vector itself; every sampled row must match the
 device result to the bit (real and imaginary parts as separate IEEE doubles; the reference has no fused multiply-add, and the kernel's
 fma for power-of-two amplitudes is exact)."""
-from math import comb
-
 import numpy as np
 import pytest
 
+from rows_ref import rank, sample_rows, unrank
+
 pytestmark = pytest.mark.gpu
-
-
-def unrank(rows, L, nup):
-    """configurations (uint64, site i = bit i-1) of 0-based rows in the reference order: site 1 up first"""
-    idx = rows.astype(np.int64).copy()
-    r = np.full(idx.shape, nup, dtype=np.int64)
-    s = np.zeros(idx.shape, dtype=np.uint64)
-    table = np.array([[comb(n, k) for k in range(nup + 1)] for n in range(L + 1)], dtype=np.int64)
-    for k in range(1, L + 1):
-        c = np.where(r > 0, table[L - k, np.maximum(r - 1, 0)], 0)
-        up = (r > 0) & (idx < c)
-        s |= np.where(up, np.uint64(1) << np.uint64(k - 1), np.uint64(0))
-        idx = np.where(up | (r == 0), idx, idx - c)
-        r = r - up
-    assert (r == 0).all()
-    return s
-
-
-def rank(s, L, nup):
-    idx = np.zeros(s.shape, dtype=np.int64)
-    r = np.full(s.shape, nup, dtype=np.int64)
-    table = np.array([[comb(n, k) for k in range(nup + 1)] for n in range(L + 1)], dtype=np.int64)
-    for k in range(1, L + 1):
-        bit = ((s >> np.uint64(k - 1)) & np.uint64(1)).astype(bool)
-        add = np.where(~bit & (r > 0), table[L - k, np.maximum(r - 1, 0)], 0)
-        idx += add
-        r = r - bit
-    assert (r == 0).all()
-    return idx
-
-
-def sample_rows(model, n_random, seed):
-    N = model.N
-    rng = np.random.default_rng(seed)
-    parts = [np.arange(0, min(N, 2048)), np.arange(max(0, N - 2048), N), rng.integers(0, N, n_random)]
-    gb = []
-    if model.device_path == "tiled":                      # tile boundaries of the device plan: rows on both sides of a few hundred of them
-        _lb, gb, _ln = model.local_tiles()
-    pick = rng.choice(len(gb), size=min(len(gb), 300), replace=False) if len(gb) else []     # (the per-row path has no tiles)
-    for t in pick:
-        parts.append(np.arange(max(0, gb[t] - 3), min(N, gb[t] + 3)))
-    return np.unique(np.concatenate(parts).astype(np.int64))
 
 
 CASES = [

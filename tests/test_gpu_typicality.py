@@ -322,14 +322,18 @@ def test_full_size_sum_rule_and_current_conservation(pkg):
     ref_jj, _, _ = R.dqt_sample(H, Jop, Jop, beta, r, times, Ebounds=Eb)
     jj = pkg.dqt_sample(m, beta, ("current", None), ("current", None), times, r=r, Ebounds=Eb)
     drift = np.abs(jj["num"] - jj["num"][0]).max() / abs(jj["num"][0])
+    dev_jj = np.abs(jj['num'] - ref_jj[:, 0]).max()
     print(f"L=20: C_JJ = {jj['num'][0].real:.6f}, drift {drift:.2e} (reference {np.abs(ref_jj - ref_jj[0]).max() / abs(ref_jj[0, 0]):.2e}), "
-          f"vs reference {np.abs(jj['num'] - ref_jj[:, 0]).max():.2e}")
+          f"vs reference {dev_jj:.2e}")
     assert drift <= 10 * 2.9e-15
+    assert dev_jj <= 1e-12 * op_norm(("current", None), L, hop) ** 2          # 1e-12 |A| |B|, the base term of check_sample
     ref_zz, _, _ = R.dqt_sample(H, R.Operator("Sz_all", None, L, states), R.Operator("Sz", 2, L, states), beta, r, times, Ebounds=Eb)
     zzc = pkg.dqt_sample(m, beta, "Sz_all", ("Sz", 2), times, r=r, Ebounds=Eb)
     res = np.abs(zzc["num"].sum(axis=1)).max()
-    print(f"L=20: sum rule residual {res:.2e} (reference {np.abs(ref_zz.sum(axis=1)).max():.2e}), vs reference {np.abs(zzc['num'] - ref_zz).max():.2e}")
+    dev_zz = np.abs(zzc['num'] - ref_zz).max()
+    print(f"L=20: sum rule residual {res:.2e} (reference {np.abs(ref_zz.sum(axis=1)).max():.2e}), vs reference {dev_zz:.2e}")
     assert res <= 10 * 3.7e-17
+    assert dev_zz <= 1e-12 * 0.5 * op_norm(("Sz", 2), L, hop)                  # |S^z_i| = |S^z_j| = 1/2
 
 
 def test_all_sectors_against_the_full_space_trace(pkg):
