@@ -142,10 +142,14 @@ static int count_nn_hops(const sd_model *m) {
 // those bonds -- the first far bonds it processes, right after its own rows were fetched by the partner -- hit
 // that XCD's L2 (or merge with the in-flight fetch) instead of going to the fabric again.  FO = max f; plans without
 // orbits (too few tiles, p < 3, no chain) deal runs of CH consecutive tiles to each XCD.  Speed only: a bijection of the tile list.
-static void xcd_order(const sd_model *m, int p, std::vector<uint32_t> &tp_io, std::vector<int64_t> &tb_io,
-                      std::vector<int64_t> &first_seen) {
+// xcd_queues returns the eight queues (entries index tp); xcd_order interleaves them, position j of queue x -> block 8j + x.
+// FO: one XCD order per length class (xcd_order): 5 beats 6 by 1 % at L=28..32 (profiles/ablation_r02.md §14); all tile lengths in
+// one launch (the block table of sd_build_plan): 6 beats 5 by 2.4 %, L=32 ComplexF64 10.97 -> 10.71 ms (profiles/ablation_packed_launch.md).
+static const int XCD_FO_CLASSES = 5, XCD_FO_PACKED = 6;
+static std::vector<std::vector<size_t>> xcd_queues(const sd_model *m, int p, const std::vector<uint32_t> &tp_io,
+                                                   std::vector<int64_t> &first_seen, const int FO) {
+  std::vector<std::vector<size_t>> q(8);
   {
-    const int FO = 5;     // measured with 5 workgroups per CU in flight (profiles/ablation_r02.md §14): 5 beats 6 by 1 % at L=28..32
     const int CH = 32;
     const size_t nt = tp_io.size();
     // (Tried: the "transposed" order -- tiles sorted by (filling of the prefix, prefix as an integer: site 1 varies fastest), dealt to
@@ -179,8 +183,7 @@ static void xcd_order(const sd_model *m, int p, std::vector<uint32_t> &tp_io, st
       std::vector<size_t> idx(nt);
       for (size_t k = 0; k < nt; ++k) idx[k] = k;
       std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
-      // deal whole orbits to the 8 XCD queues, then interleave the queues (position j of queue x -> block 8j + x)
-      std::vector<std::vector<size_t>> q(8);
+      // deal whole orbits to the 8 XCD queues
       size_t o = 0;
       for (size_t k = 0; k < nt;) {
         size_t e = k;
@@ -188,30 +191,35 @@ static void xcd_order(const sd_model *m, int p, std::vector<uint32_t> &tp_io, st
         for (size_t t = k; t < e; ++t) q[o % 8].push_back(idx[t]);
         ++o; k = e;
       }
-      std::vector<uint32_t> tp; std::vector<int64_t> tb;
-      tp.reserve(nt); tb.reserve(nt);
-      size_t longest = 0;
-      for (auto &v : q) longest = std::max(longest, v.size());
-      for (size_t j = 0; j < longest; ++j)
-        for (int x = 0; x < 8; ++x)
-          if (j < q[x].size()) { tp.push_back(tp_io[q[x][j]]); tb.push_back(tb_io[q[x][j]]); }
       for (size_t k = 0; k < nt; ++k) first_seen_reset(tp_io[k]);
-      tp_io.swap(tp); tb_io.swap(tb);
-    } else if (nt >= (size_t)16 * CH) {
-      std::vector<uint32_t> tp(nt);
-      std::vector<int64_t> tb(nt);
-      const size_t group = (size_t)8 * CH, full = nt / group * group;
+    } else {
+      // runs of CH consecutive tiles per queue (long lists), or the list as it is (block b = tile b: queue b % 8)
+      const size_t group = (size_t)8 * CH, full = nt >= (size_t)16 * CH ? nt / group * group : 0;
       for (size_t b = 0; b < nt; ++b) {
         size_t t = b;
         if (b < full) {
           const size_t x = b % 8, sl = b / 8, g = sl / CH, i = sl % CH;
           t = g * group + x * CH + i;
         }
-        tp[b] = tp_io[t]; tb[b] = tb_io[t];
+        q[b % 8].push_back(t);
       }
-      tp_io.swap(tp); tb_io.swap(tb);
     }
   }
+  return q;
+}
+
+static void xcd_order(const sd_model *m, int p, std::vector<uint32_t> &tp_io, std::vector<int64_t> &tb_io,
+                      std::vector<int64_t> &first_seen) {
+  const std::vector<std::vector<size_t>> q = xcd_queues(m, p, tp_io, first_seen, XCD_FO_CLASSES);
+  const size_t nt = tp_io.size();
+  std::vector<uint32_t> tp; std::vector<int64_t> tb;
+  tp.reserve(nt); tb.reserve(nt);
+  size_t longest = 0;
+  for (auto &v : q) longest = std::max(longest, v.size());
+  for (size_t j = 0; j < longest; ++j)
+    for (int x = 0; x < 8; ++x)
+      if (j < q[x].size()) { tp.push_back(tp_io[q[x][j]]); tb.push_back(tb_io[q[x][j]]); }
+  tp_io.swap(tp); tb_io.swap(tb);
 }
 
 // ---- ownership by nested bisections of popcount cells (nranks = 2, 4, 8) ----
@@ -815,6 +823,85 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
         m->single_prefix.push_back(short_p[k]); m->single_base.push_back(short_b[k]);
         if (pass == 0) ++m->n_short_multi;
       }
+    // Block table of the packed ComplexF64 launch (k_apply_tiled, PACK): the class launches above bought their wave utilisation
+    // with one launch per class, each XCD-ordered on its own -- tiles that were queue neighbours (an orbit's straddle siblings have
+    // another length; the lexicographic neighbours on the adjacent XCD queues) then run milliseconds apart.  Here all non-short
+    // tiles are XCD-ordered TOGETHER, as before the classes existed, and each of the eight queues is packed next-fit, in queue
+    // order, into workgroups of four 256-row wave slots: a tile takes ceil(len / 256) consecutive slots of one block, is never
+    // split across blocks, and the order inside a queue is never permuted.  Block j of queue x becomes block 8j + x as long as all
+    // eight queues last; where a queue has run out the others close ranks, as in xcd_order, so the tail of the launch is still dealt
+    // to all eight XCDs (padding the short queues with idle blocks instead left their XCDs without work at the end: +0.5 %).  Orbit
+    // members have equal length, so orbits pack densely.  The entries index single_rec: tile records, far_base rows and partial-sum slots
+    // stay where they are, and Float64 keeps the class launches on the same plan.  Unsharded chain-bond plans with the packed
+    // partner tables only (sd_upload_model drops the table when a wrap bond or a general-bond plan is in use).
+    // Not where one-slot tiles (at most 256 rows) hold more than an eighth of the rows -- sectors away from half filling: such a
+    // tile ran in a one-wave workgroup of its own at seven waves per SIMD (71 registers) and runs here at six, tied to three
+    // unrelated tiles by the block's barrier and life time.  Half filling at L=32: 6.6 % of the rows, the packed launch wins 2 %;
+    // L=34 nup=12 (29 %) and L=36 nup=9 (56 %) keep the class launches (profiles/ablation_packed_launch.md section 7).
+    // SD_LEN_CLASSES=2 (tests) packs whatever the share.
+    m->blk_tiles.clear();
+    bool pack = nranks == 1 && split && m->LS <= 12 && p >= 1 && m->short_off > 0;
+    if (pack) {
+      const char *e = getenv("SD_LEN_CLASSES");
+      if (!(e && atoi(e) >= 2)) {
+        int64_t rows_one = 0, rows_all = 0;
+        for (int k = 0; k < m->short_off; ++k) {
+          const int64_t len = B(m, m->LS, m->nup - __builtin_popcount(m->single_prefix[k]));
+          rows_all += len;
+          if (len <= 256) rows_one += len;
+        }
+        pack = 8 * rows_one <= rows_all;
+      }
+    }
+    if (pack) {
+      std::vector<int32_t> index_of((size_t)1 << p, -1);        // prefix -> index in single_rec
+      for (int k = 0; k < m->short_off; ++k) index_of[m->single_prefix[k]] = k;
+      // the non-short tiles in natural order (= ascending base: the order the tile list had before any XCD ordering)
+      std::vector<std::pair<int64_t, uint32_t>> by_base((size_t)m->short_off);
+      for (int k = 0; k < m->short_off; ++k) by_base[k] = {m->single_base[k], m->single_prefix[k]};
+      std::sort(by_base.begin(), by_base.end());
+      std::vector<uint32_t> all((size_t)m->short_off);
+      for (int k = 0; k < m->short_off; ++k) all[k] = by_base[k].second;
+      const std::vector<std::vector<size_t>> q = xcd_queues(m, p, all, xcd_scratch, XCD_FO_PACKED);
+      auto slots_of = [&](uint32_t P) { return (int)((B(m, m->LS, m->nup - __builtin_popcount(P)) + 255) / 256); };
+      std::vector<std::vector<int32_t>> qb(8);                  // per queue: its blocks, four entries each
+      for (int x = 0; x < 8; ++x) {
+        int used = 4;                                          // slots taken in the queue's last block
+        for (size_t t : q[x]) {
+          const int ns_t = slots_of(all[t]);
+          if (ns_t < 1 || ns_t > 4) { err = "block table: tile longer than a workgroup"; return SD_EINTERNAL; }
+          if (used + ns_t > 4) { qb[x].insert(qb[x].end(), 4, -1); used = 0; }
+          for (int s = 0; s < ns_t; ++s) qb[x][qb[x].size() - 4 + (size_t)(used + s)] = index_of[all[t]];
+          used += ns_t;
+        }
+      }
+      size_t longest = 0;
+      for (auto &v : qb) longest = std::max(longest, v.size() / 4);
+      for (size_t j = 0; j < longest; ++j)
+        for (int x = 0; x < 8; ++x)
+          if (j < qb[x].size() / 4) m->blk_tiles.insert(m->blk_tiles.end(), qb[x].begin() + 4 * j, qb[x].begin() + 4 * j + 4);
+      // self-check, O(tiles): every non-short tile in exactly one block, in consecutive slots, with the right slot count.  A guard
+      // against a slip in the packing loop above (it shares slots_of with it), nothing more: that a team fits its block's LDS
+      // image follows from the record having four slots, not from this check.
+      std::vector<int32_t> seen((size_t)m->short_off, 0);
+      bool ok = true;
+      for (size_t b = 0; b < m->blk_tiles.size() / 4 && ok; ++b) {
+        const int32_t *bt = m->blk_tiles.data() + 4 * b;
+        for (int s = 0; s < 4 && ok; ++s) {
+          const int32_t t = bt[s];
+          if (t == -1) continue;
+          if (t < 0 || t >= m->short_off) { ok = false; break; }
+          if (s > 0 && bt[s - 1] == t) continue;               // counted at the team's first slot
+          int run = 1;
+          while (s + run < 4 && bt[s + run] == t) ++run;
+          for (int s2 = s + run; s2 < 4; ++s2) if (bt[s2] == t) ok = false;      // not consecutive
+          if (seen[t] != 0 || run != slots_of(m->single_prefix[t])) ok = false;
+          seen[t] = 1;
+        }
+      }
+      for (int k = 0; k < m->short_off && ok; ++k) if (!seen[k]) ok = false;
+      if (!ok) { m->blk_tiles.clear(); err = "block table of the packed launch failed its self-check"; return SD_EINTERNAL; }
+    }
   }
   m->tile_gbase.resize(m->tile_prefix.size());
   for (size_t k = 0; k < m->tile_prefix.size(); ++k) m->tile_gbase[k] = tile_base_global(m, m->tile_prefix[k]);
@@ -921,6 +1008,7 @@ int sd_upload_model(sd_model *m, std::string &err) {
     d.n_singles = (int)m->single_prefix.size();
     d.n_interior = m->n_interior; d.tile_off = 0;
     d.n_short = m->n_short; d.short_off = m->short_off; d.n_short_multi = m->n_short_multi;
+    d.n_blk = 0; d.blk_tiles = nullptr;        // (set below, once the wrap bond and the general-bond plan are known)
     m->single_rec.resize(m->single_prefix.size());
     for (size_t k = 0; k < m->single_prefix.size(); ++k) {
       const uint32_t P = m->single_prefix[k];
@@ -1010,6 +1098,11 @@ int sd_upload_model(sd_model *m, std::string &err) {
         d.n_gen = (int)m->gen.size();
         d.wrap_hop = -1;                                   // the wrap bond, if any, is one of the plan's mixed bonds
       }
+    }
+    // the packed launch: chain bonds and per-row general bonds only -- no wrap bond, no general-bond plan
+    if (!m->blk_tiles.empty() && d.suf_part && d.wrap_hop < 0 && d.n_gen == 0) {
+      if ((rc = up(m, m->blk_tiles, &d.blk_tiles, err))) return rc;
+      d.n_blk = (int)(m->blk_tiles.size() / 4);
     }
   }
   // General couplings (no exact shortcut for the diagonal): the reference's sequential sum of up to 2L-1 rounded terms per

@@ -17,7 +17,8 @@
 //    prefix spaces): one row per thread, combinadic unrank / rank per hop.
 // sd_launch_apply picks the path and, for tiled plans with many tiles, issues one
 // launch per tile length class (64 / 128 / 256 / 512 / 1024 threads) and per part
-// (interior / boundary tiles of a sharded plan).
+// (interior / boundary tiles of a sharded plan) -- or, for ComplexF64 on an unsharded
+// chain plan with a block table, ONE launch of the packed form for all tile lengths.
 //
 // Per-row operation order follows the reference exactly (fields, zz in list
 // order, value = diag*psi[idx], then hops in list order, value += J*psi[idx'])
@@ -67,7 +68,18 @@ namespace {
 // 16-byte load per row, L2/L1 resident: 64 KB for all sectors): a bond costs a shift, a mask, an LDS read and the
 // multiply-add -- the binomial form (!PK: popcount, LDS binomial look-up, two bit tests, signed offset, select) cost ~14
 // lane-operations per row and bond, half of the kernel's VALU stream (VERDICT r03, weak point 5).
-template <int NC, int R, int BLOCK, bool FMA, bool PK, bool GEN = false>
+//
+// PACK (ComplexF64, unsharded chain plans whose length classes are split): ONE launch for all tile lengths.  A workgroup is four
+// wave slots of 256 rows; the block table dm.blk_tiles (basis.cpp) names the tile of every slot, a tile of len rows holding
+// ceil(len / 256) consecutive slots of one block (its TEAM of waves), -1 an idle slot.  A wave finds its tile, its index inside the
+// team and the team's first slot from the block record (scalar values); the team's LDS image starts at first_slot * 257 rows, so
+// every tile of the block keeps its own zero row.  Everything after that is per wave and the code of the 128- and 256-thread class
+// launches; a tile of at most 256 rows differs from its 64-thread class form: six waves per SIMD instead of seven, no skipping of
+// dead row groups, a barrier shared with three unrelated tiles -- which is why plans where such tiles hold more than an eighth of
+// the rows keep the class launches (sd_build_plan).  The blocks run in the XCD order of ALL tiles together, while a 220-row tile
+// still occupies one wave only.  An idle slot runs as a
+// tile of no rows (every load is out of range, nothing is stored), so all four waves meet at the barriers.
+template <int NC, int R, int BLOCK, bool FMA, bool PK, bool GEN = false, bool PACK = false>
 __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_tiled(sd_dev_model dm, double *__restrict__ out_,
                                                        const double *__restrict__ psi_, int epi, sd_epi_args ea,
                                                        double *__restrict__ partials, int max_len) {
@@ -75,9 +87,11 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   constexpr uint32_t ES = sizeof(V);
   constexpr int WR = R * 64;                                   // rows of a wave
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  static_assert(!PACK || (PK && !GEN && R == 4 && BLOCK == 256), "packed launch: four slots of 256 rows, packed tables, chain bonds");
+  constexpr int SLOT_ROWS = WR + 1;                            // PACK: LDS rows of a wave slot (its own zero row + 256 rows)
   V *tile = reinterpret_cast<V *>(smem);                       // row 0: all zero; rows 1..len: the tile's psi
   int *lbin = reinterpret_cast<int *>(smem + (size_t)(max_len + 1) * sizeof(V));   // !PK only
-  double *red = reinterpret_cast<double *>(lbin + 16 * SD_BIN_STRIDE);
+  double *red = PACK ? reinterpret_cast<double *>(smem + (size_t)(4 * SLOT_ROWS) * sizeof(V)) : reinterpret_cast<double *>(lbin + 16 * SD_BIN_STRIDE);
   V *tile2 = reinterpret_cast<V *>(red + 32);                  // wrap bond (dm.wrap_hop): row 0 zero, rows 1.. the partner tile
 
   if (ea.batch > 1) {                                          // vector blockIdx.y of a batch (sd_epi_args::batch)
@@ -93,13 +107,34 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   const V *__restrict__ halo = reinterpret_cast<const V *>(ea.halo);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int i0 = (tid >> 6) * WR + lane;                       // the thread's first row; row group r: i0 + 64 r
-  const int tix = blockIdx.x + dm.tile_off;
-  const sd_tile_rec rec = dm.single_rec[tix];       // one 32-byte scalar load: no dependent table look-ups at start-up
+  // PACK: the wave's slot, from the block record (wave-uniform: one 16-byte scalar load, the rest scalar compares)
+  int slot_tile = 0, team_wave = 0, team_n = 1, wv = 0;
+  bool idle = false;
+  if constexpr (PACK) {
+    wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    typedef int i4 __attribute__((ext_vector_type(4)));
+    const i4 bt = *reinterpret_cast<const i4 *>(dm.blk_tiles + 4 * (size_t)blockIdx.x);
+    const int st[4] = {bt.x, bt.y, bt.z, bt.w};
+    slot_tile = __builtin_amdgcn_readfirstlane(wv == 0 ? st[0] : wv == 1 ? st[1] : wv == 2 ? st[2] : st[3]);
+    team_n = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (st[k] == slot_tile) ++team_n;
+      if (st[k] == slot_tile && k < wv) ++team_wave;          // a team's slots are consecutive
+    }
+    team_wave = __builtin_amdgcn_readfirstlane(team_wave);
+    team_n = __builtin_amdgcn_readfirstlane(team_n);
+    idle = slot_tile < 0;
+    tile += (wv - team_wave) * SLOT_ROWS;                      // the team's image
+  }
+  const int i0 = (PACK ? team_wave : (tid >> 6)) * WR + lane;  // the thread's first row; row group r: i0 + 64 r
+  const int tix = PACK ? (idle ? 0 : slot_tile) : blockIdx.x + dm.tile_off;
+  const sd_tile_rec rec = dm.single_rec[tix];       // one 32-byte scalar load (PACK: after the block record; a per-slot copy of the record that
+                                                    // spares the dependent load was measured and changes nothing: profiles/ablation_packed_launch.md)
   const uint32_t P = rec.prefix;
   const int64_t base = rec.base;
   const int p = dm.p, LS = dm.LS;
-  const int len = rec.len;
+  const int len = (PACK && idle) ? 0 : rec.len;     // (an idle slot: no rows, whatever record it read)
   const int nU = rec.nU;                            // rows whose first suffix site is up
   const int nn = dm.nn_hops;
   // GEN: the model's general bonds run from the host-resolved plan dm.gen (section 4b); the suffix configurations are then needed
@@ -141,7 +176,7 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   uint64_t fmask = 0;
   int64_t my_base = -1;
   const uint32_t bitp = p >= 1 ? ((P >> (p - 1)) & 1u) : 0u;
-  if (nn > 0 && p >= 1) {
+  if (nn > 0 && p >= 1 && !(PACK && idle)) {
     const int b = lane + 1;
     if (b <= p) my_base = dm.far_base[(size_t)tix * (size_t)p + (size_t)lane];
     fmask = __ballot(my_base >= 0);
@@ -162,6 +197,9 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   // cycles (TA busy 70 % of the launch, ablation_r03.md section 5).
   // Float64: measured -2...3 % there, but +5 % for ComplexF64 (round 3) -- except in the one-wave workgroups of the short tiles
   // (dilute sectors: most tiles fill one or two row groups; profiles/ablation_r04.md).
+  // (PACK: its one-slot teams are such one-wave tiles, but the skip, carried into them through a wave-uniform branch on the team
+  // size, costs the form 79 instead of 73 registers and 0.09 ms at L=32 half filling and gains nothing in the dilute sectors either,
+  // which keep the one-wave class launches anyway -- sd_build_plan; profiles/ablation_packed_launch.md section 7.)
   constexpr bool SKIP_DEAD = NC == 1 || BLOCK == 64;
   uint32_t live = 0;
   if (SKIP_DEAD) {
@@ -228,7 +266,7 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
 #pragma unroll
   for (int r = 0; r < R; ++r)
     if (i0 + r * 64 < len) tile[1 + i0 + r * 64] = own[r];
-  if (tid == 0) tile[0] = V{};         // the zero row read by lanes whose suffix bond is not flippable
+  if (PACK ? (lane == 0 && team_wave == 0) : (tid == 0)) tile[0] = V{};         // the zero row read by lanes whose suffix bond is not flippable
   if (!PK)
     for (int k = tid; k < 16 * SD_BIN_STRIDE; k += BLOCK) {
       int n = k / SD_BIN_STRIDE, kk = k - n * SD_BIN_STRIDE;
@@ -266,7 +304,7 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   // address unit pays per line (+19 % on the apply).  The partner tile is streamed instead, coalesced like a far bond, into a
   // second LDS image (the stream registers are free now) and read there after the suffix bonds, at the row the packed table names.
   // (not for the 8-row Float64 form: its 96 registers -- five waves -- have no room, the code would spill; it keeps the gather)
-  const bool wrap = !GEN && PK && !(NC == 1 && R == 8) && nn > 0 && dm.wrap_hop == nn;
+  const bool wrap = !GEN && !PACK && PK && !(NC == 1 && R == 8) && nn > 0 && dm.wrap_hop == nn;
   bool wrap_on = false;
   if (wrap) {
     const uint32_t Q = P ^ (1u << dm.wrap_pb);
@@ -526,9 +564,25 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   }
   if (epi_has_sums(epi)) {
     double a = sums.s0, b = sums.s1;
-    block_reduce2(a, b, red);
-    // one pair per tile of the plan (interior and boundary launches fill disjoint slots of one buffer sized for all tiles)
-    if (tid == 0) { partials[2 * (size_t)tix] = a; partials[2 * (size_t)tix + 1] = b; }
+    if constexpr (PACK) {
+      // per team what block_reduce2 does in a workgroup of the team's size: every wave by shuffles, its pair filed under its slot,
+      // then the team's pairs added in ascending wave order -- the tile's partial sums have the bits of the class launches
+      for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_down(a, off, 64);
+        b += __shfl_down(b, off, 64);
+      }
+      if (lane == 0) { red[2 * wv] = a; red[2 * wv + 1] = b; }
+      __syncthreads();
+      if (lane == 0 && team_wave == 0 && !idle) {
+        double x = 0.0, y = 0.0;
+        for (int w = 0; w < team_n; ++w) { x += red[2 * (wv + w)]; y += red[2 * (wv + w) + 1]; }
+        partials[2 * (size_t)tix] = x; partials[2 * (size_t)tix + 1] = y;
+      }
+    } else {
+      block_reduce2(a, b, red);
+      // one pair per tile of the plan (interior and boundary launches fill disjoint slots of one buffer sized for all tiles)
+      if (tid == 0) { partials[2 * (size_t)tix] = a; partials[2 * (size_t)tix + 1] = b; }
+    }
   }
 }
 
@@ -937,10 +991,10 @@ int sd_launch_epilogue_only(sd_ctx *ctx, int dtype, int64_t n, void *out, const 
 }
 namespace {
 
-template <int NC, int R, int BLOCK, bool FMA, bool PK, bool GEN = false>
+template <int NC, int R, int BLOCK, bool FMA, bool PK, bool GEN = false, bool PACK = false>
 int launch_tiled_cfg(sd_ctx *ctx, const sd_dev_model &dm, int nt, size_t shmem, double *out, const double *psi, int epi,
                      const sd_epi_args &ea, int max_len) {
-  void (*kern)(sd_dev_model, double *, const double *, int, sd_epi_args, double *, int) = k_apply_tiled<NC, R, BLOCK, FMA, PK, GEN>;
+  void (*kern)(sd_dev_model, double *, const double *, int, sd_epi_args, double *, int) = k_apply_tiled<NC, R, BLOCK, FMA, PK, GEN, PACK>;
   // per kernel AND per device, so no cache: cheap next to a launch, and only the SD_SUFFIX_BITS >= 13 tiles get here
   if (shmem > 48 * 1024)
     SD_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
@@ -1012,8 +1066,16 @@ int sd_launch_apply(sd_ctx *ctx, const sd_model *m, int dtype, void *out, const 
     const size_t esz = dtype == SD_C128 ? 16 : 8;
     int rc = SD_OK;
     if (nt > 0) {
-      // one launch per non-empty (part, tile length class) segment; a segment's LDS image is sized by its own longest tile
-      const int s0 = part == 2 ? SD_N_LEN_CLASS : 0, s1 = part == 1 ? SD_N_LEN_CLASS : 2 * SD_N_LEN_CLASS;
+      // ComplexF64 on a plan with a block table: all tile lengths in one launch, four wave slots per workgroup (k_apply_tiled,
+      // PACK); four images of 1 + 256 rows and the reduction scratch.  Then the short tiles and the reduction as always.
+      const bool packed = part == 0 && dtype == SD_C128 && dm.n_blk > 0;
+      if (packed) {
+        const size_t shmem = (size_t)4 * 257 * esz + 32 * sizeof(double) + 16;
+        rc = m->hop_pow2 ? launch_tiled_cfg<2, 4, 256, true, true, false, true>(ctx, dm, dm.n_blk, shmem, (double *)out, (const double *)psi, epi, ea, 1024)
+                         : launch_tiled_cfg<2, 4, 256, false, true, false, true>(ctx, dm, dm.n_blk, shmem, (double *)out, (const double *)psi, epi, ea, 1024);
+      }
+      // otherwise one launch per non-empty (part, tile length class) segment; a segment's LDS image is sized by its own longest tile
+      const int s0 = part == 2 ? SD_N_LEN_CLASS : 0, s1 = packed ? s0 : part == 1 ? SD_N_LEN_CLASS : 2 * SD_N_LEN_CLASS;
       for (int sg = s0; sg < s1 && rc == SD_OK; ++sg) {
         const int cnt = m->seg_off[sg + 1] - m->seg_off[sg];
         if (cnt <= 0) continue;

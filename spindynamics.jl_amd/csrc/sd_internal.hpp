@@ -163,6 +163,11 @@ struct sd_dev_model {
   // per lane, partner rows by the closed form of the combinadic order instead of a workgroup per tile.  n_short = 0: none.
   int n_short, short_off;
   int n_short_multi;             // the first n_short_multi of them hold 2..16 rows (sixteen lanes per tile), the rest one row (one lane per tile)
+  // Block table of the packed ComplexF64 launch (k_apply_tiled, PACK; built by sd_build_plan for unsharded chain plans with the packed
+  // partner tables whose length classes are split): n_blk records of four wave slots, each the single_rec index of the slot's tile or
+  // -1 (idle); a tile of len rows holds ceil(len / 256) consecutive slots of one record.  n_blk = 0: no table, one launch per class.
+  int n_blk;
+  const int32_t *blk_tiles;
 };
 
 #define SD_N_LEN_CLASS 5   // tile length classes: workgroups of 64, 128, 256, 512, 1024 threads (x 4 rows)
@@ -210,6 +215,7 @@ struct sd_model {
   int seg_cls[2 * SD_N_LEN_CLASS] = {0};       // workgroup size of a segment's kernel = 64 << seg_cls
   std::vector<int64_t> single_base;
   std::vector<sd_tile_rec> single_rec;
+  std::vector<int32_t> blk_tiles;              // block table of the packed launch (see sd_dev_model), 4 entries per block; empty: none
   int max_tile_len = 0;        // longest OWNED tile
   int max_tile_len_all = 0;    // longest tile of the whole basis (a partner tile imported from a peer may be longer than any owned one)
   bool hop_pow2 = false;  // every NN hop amplitude is +-2^k (or 0): J*psi is exact, fma == mul+add
