@@ -377,6 +377,20 @@ int sd_connected_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, con
 /* structure_factor_Sq   src/Observables.jl:100-109 : q_out[k] = 2 pi k / L, S_out[k] = real(fft(C_r))[k] */
 int sd_structure_factor(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, double *q_out, double *S_out);
 int sd_structure_factor_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, double *q_out, double *S_out);
+/* Equal-time pair correlations of one state, all L x L site pairs from one call (sites 1-based; nothing is divided by <psi|psi>,
+ * as in the observables above):
+ *   SD_PAIR_PM: G_ij = <psi| S^+_i S^-_j |psi> = sum over rows s with site j up and site i down of conj(psi[s']) psi[s], s' = s with
+ *               the up spin moved from j to i.  Hermitian; G_ii = sum_s |psi[s]|^2 [site i up] = <psi|psi>/2 + <S^z_i>; complex for
+ *               a ComplexF64 psi, imaginary parts exactly 0 for a Float64 psi.  <S^-_i S^+_j> = conj(G_ij) for i != j and
+ *               <psi|psi>/2 - <S^z_i> for i == j, in a sector and in the full basis alike.
+ *   SD_PAIR_ZZ: Z_ij = <psi| S^z_i S^z_j |psi>; real symmetric, Z_ii = <psi|psi>/4, imaginary parts 0.
+ * M_out: 2 L L host doubles, (re, im) of M[i-1][j-1] row-major, both triangles and the diagonal.  Fixed-nup sectors and the full
+ * basis; unsharded models only (SD_EARG), a wrong n is SD_EDIM.  Sums in a fixed order: the same call gives the same bits.
+ * _dev: psi is a device pointer; the call synchronises the stream. */
+#define SD_PAIR_ZZ 0
+#define SD_PAIR_PM 1
+int sd_pair_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int component, double *M_out);
+int sd_pair_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int component, double *M_out);
 /* create_spin_operator(site, op)(psi, model)   src/Hamiltonian.jl:49-136.  site is 1-based.  S^z is diagonal and works
  * in any basis; S^+, S^-, S^x, S^y change the magnetisation and are rejected in a fixed-nup sector (SD_EARG), as the
  * reference does.  out has psi's element type; S^y needs a ComplexF64 psi (SD_EARG otherwise: the reference's

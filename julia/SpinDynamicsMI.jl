@@ -21,7 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
-       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, typicality_sample, typicality_correlation_function,
+       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, pair_correlations, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -494,6 +494,17 @@ function current_expectation(bra::AbstractVector, ket::AbstractVector, model::Mo
                 (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}),
                 model.ctx.h, model.h, dtype_code(eltype(b)), b, k, length(k), w, out), model.ctx.h)
     return complex(out[1], out[2])
+end
+
+# Equal-time pair correlations of psi for all site pairs (DESIGN.md 15): component :pm gives <S^+_i S^-_j>, :zz gives <S^z_i S^z_j>;
+# L x L ComplexF64, nothing divided by <psi|psi>
+function pair_correlations(psi::AbstractVector, model::Model; component::Symbol=:zz)
+    component in (:zz, :pm) || throw(ArgumentError("component must be :zz or :pm"))
+    p = hostvec(psi)
+    out = Vector{Float64}(undef, 2 * model.L * model.L)
+    check(ccall((:sd_pair_correlations, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), component === :pm ? 1 : 0, out), model.ctx.h)
+    return permutedims(reshape(reinterpret(ComplexF64, out), model.L, model.L))     # the ABI is row-major
 end
 
 # operator descriptors: (:Sz, site), (:Szq, q), :Sz_all (operator_i only), (:current, weights | nothing) -> (kind, parameter, weights)

@@ -148,6 +148,8 @@ PROTOTYPES = {
     "sd_current_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _dp, _vp]),
     "sd_current_bracket": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _dp, _dp]),
     "sd_current_bracket_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _dp, _dp]),
+    "sd_pair_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _i, _dp]),
+    "sd_pair_correlations_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _dp]),
     "sd_dqt_correlations": (_i, [_vp, _vp, _d, _vp, _u64, _i, _d, _dp, _i, _d, _dp, _dp, _i, _i, _i, _i, _d, _d, _dp, _dp, _dp, _dp]),
     "sd_magnetization": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),
     "sd_magnetization_dev": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),

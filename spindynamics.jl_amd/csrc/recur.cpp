@@ -1795,6 +1795,39 @@ int current_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, con
   return SD_OK;
 }
 
+// M_out (host, 2 L L doubles) = the L x L pair-correlation matrix of psi: the kernel sums the pairs i <= j, the other triangle is
+// the conjugate
+int pair_correlations_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int component, double *M_out,
+                           bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (component != SD_PAIR_ZZ && component != SD_PAIR_PM) return sd_set_err(ctx, SD_EARG, "component must be SD_PAIR_ZZ or SD_PAIR_PM");
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!M_out) return sd_set_err(ctx, SD_EARG, "null argument");
+  DBuf in, plist, res;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
+  const int L = m->L;
+  std::vector<int> pairs;
+  for (int i = 0; i < L; ++i)
+    for (int j = i; j < L; ++j) pairs.push_back(i | (j << 8));
+  const int np = (int)pairs.size();
+  RC(plist.alloc(ctx, (np + 1) / 2));
+  RC(sd_xfer_h2d(ctx, plist.p, pairs.data(), sizeof(int) * (size_t)np));
+  RC(res.alloc(ctx, 2 * (int64_t)np));
+  RC(sd_launch_pair_correlations(ctx, m, dtype, p, component, (const int *)plist.p, np, res.p));
+  std::vector<double> h(2 * (size_t)np);
+  SD_HIP(ctx, hipMemcpyAsync(h.data(), res.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < np; ++k) {
+    const int i = pairs[k] & 255, j = pairs[k] >> 8;
+    const double re = h[2 * (size_t)k], im = h[2 * (size_t)k + 1];
+    double *a = M_out + 2 * ((size_t)i * L + j), *b = M_out + 2 * ((size_t)j * L + i);
+    b[0] = re; b[1] = im == 0.0 ? 0.0 : -im;
+    a[0] = re; a[1] = im;
+  }
+  return SD_OK;
+}
+
 // an operator of the typicality driver: kind, site or momentum, device weights of a current
 struct DqtOp {
   int kind = 0; int site = 0; double q = 0.0; DBuf wt;
@@ -1860,6 +1893,15 @@ extern "C" int sd_current_bracket_dev(sd_ctx *ctx, const sd_model *m, int dtype_
     if (!bra_dev) return sd_set_err(ctx, SD_EARG, "null argument");
     return current_core(ctx, m, dtype_bra, ket_dev, bra_dev, true, n, w, out, true);
   });
+}
+
+extern "C" int sd_pair_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int component,
+                                    double *M_out) {
+  return abi_guard(ctx, [&]() -> int { return pair_correlations_core(ctx, m, dtype, psi_host, n, component, M_out, false); });
+}
+extern "C" int sd_pair_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int component,
+                                        double *M_out) {
+  return abi_guard(ctx, [&]() -> int { return pair_correlations_core(ctx, m, dtype, psi_dev, n, component, M_out, true); });
 }
 
 extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, const void *r_host, uint64_t seed, int B_kind,

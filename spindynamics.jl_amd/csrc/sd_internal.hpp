@@ -293,6 +293,12 @@ int sd_launch_site_project(sd_ctx *ctx, const sd_model *m, int dtype_bra, const 
 int sd_launch_current(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, const double *wt_dev, void *out,
                       double *dst);
 
+// Equal-time pair correlations (kernels_pairs.hip): dst[2k .. +1] (device) = (re, im) of <psi|S^+_i S^-_j|psi> (SD_PAIR_PM) or
+// (<psi|S^z_i S^z_j|psi>, 0) (SD_PAIR_ZZ) for pair k of pairs_dev -- npairs device ints bi | bj << 8, 0-based bits, bi <= bj < L -- of
+// psi (`dtype`, device).  Nothing is divided by <psi|psi>.  Unsharded models; queued on the context's stream, deterministic.
+int sd_launch_pair_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int component, const int *pairs_dev,
+                                int npairs, double *dst);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.
