@@ -50,7 +50,7 @@ namespace {
 //      go to LDS and the only barrier follows at once (all waves are at the same
 //      point; afterwards each wave runs on its own clock);
 //   4. the far-bond partner rows are streamed with a two-deep ping-pong
-//      pipeline (loads of bond k+1 in flight while bond k is accumulated);
+//      pipeline (loads of bond k+1 in flight while bond k is accumulated; PACK: a ring with counted waits, below);
 //   5. the gathers of the first general bond (e.g. the periodic (L,1) bond) are
 //      requested into the idle stream registers; the suffix bonds are LDS reads at
 //      idx +- C(LS-a-1,u); then the general bonds;
@@ -79,6 +79,24 @@ namespace {
 // the rows keep the class launches (sd_build_plan).  The blocks run in the XCD order of ALL tiles together, while a 220-row tile
 // still occupies one wave only.  An idle slot runs as a
 // tile of no rows (every load is out of range, nothing is stored), so all four waves meet at the barriers.
+//
+// PACK, far bonds: a RING of SD_PACK_RING register sets instead of the conditional ping-pong.  One loop iteration issues the loads of
+// SD_PACK_RING consecutive entries of the far-bond list, unconditionally, and then accumulates them in list order, so the compiler
+// counts the loads in flight (s_waitcnt vmcnt(n > 0) before all but the last accumulation of an iteration).  The list is closed
+// to a multiple of the ring depth by EMPTY bonds: zero records on a valid base, J = 0 -- every lane reads 0, nothing leaves the CU,
+// and acc + J * 0 is what rows outside the straddle window do anyway.  Order and arithmetic are those of the ping-pong.
+// SD_PACK_WGS_PER_CU: workgroups of the packed launch per CU, capped through its dynamic LDS request (sd_launch_apply); 6 is what
+// the registers allow, i.e. no cap.  Fewer tiles in flight per XCD keep an orbit's partner lines in L2 until the mates re-read them;
+// the ring is what makes that affordable (the ping-pong LOSES at four workgroups, the ring gains 2 %).  Both are compile-time
+// constants with a -D override for profiles/build_variant.sh; the sweep is profiles/ablation_packed_pipeline.md.
+#ifndef SD_PACK_RING
+#define SD_PACK_RING 2
+#endif
+#ifndef SD_PACK_WGS_PER_CU
+#define SD_PACK_WGS_PER_CU 4
+#endif
+static_assert(SD_PACK_RING >= 2 && SD_PACK_RING <= 4, "ring depth of the packed launch: 2..4 register sets");
+static_assert(SD_PACK_WGS_PER_CU >= 2 && SD_PACK_WGS_PER_CU <= 6, "workgroups per CU of the packed launch: 2..6");
 template <int NC, int R, int BLOCK, bool FMA, bool PK, bool GEN = false, bool PACK = false>
 __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_tiled(sd_dev_model dm, double *__restrict__ out_,
                                                        const double *__restrict__ psi_, int epi, sd_epi_args ea,
@@ -228,7 +246,39 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   uint64_t mk = fmask;
   bool have_a = false;
   auto next_lane = [&](uint64_t &m_) { const int ln = __builtin_ctzll(m_); m_ &= m_ - 1; return ln; };   // ascending bond order
-  if (mk) { fa = get_bond(next_lane(mk)); issue(fa, va); have_a = true; }
+  // PACK: the ring.  Sets 0 and 1 are va and vb, the others vx; entry k of an iteration uses set k.
+  constexpr int D = PACK ? SD_PACK_RING : 2;
+  V vx[D > 2 ? D - 2 : 1][R];
+  FarBond fr[D];
+  int ring_iters = 0;
+  auto ring_next = [&]() {                                       // the next list entry, or an EMPTY bond once the list is used up
+    FarBond fb;
+    const bool e = mk == 0;
+    const int ln = e ? 0 : __builtin_ctzll(mk);
+    mk &= mk - 1;
+    fb.base = e ? 0 : rl64(my_base, ln);
+    fb.J = 0.0;
+    if (!e) fb.J = dm.hop_J[ln];
+    const bool st = ln == p - 1;
+    fb.lo = st ? st_lo : 0; fb.n = e ? 0 : st ? st_n : len;
+    return fb;
+  };
+  auto ring_issue = [&](const FarBond &fb, V(&v)[R]) {           // (unsharded plans only: no halo)
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(psi + fb.base, (uint32_t)fb.n * ES);
+    const uint32_t rel = off0 - (uint32_t)fb.lo * ES;
+#pragma unroll
+    for (int r = 0; r < R; ++r) buf_load(v[r], rs, rel + (uint32_t)(r * 64) * ES);
+  };
+  if constexpr (PACK) {
+    // iterations of the ring: the list length rounded up to whole rings, one at least (an idle slot, a model without hops:
+    // EMPTY bonds only), so that the first entry always goes out here, before the barrier
+    const int nf = __popcll(fmask);
+    ring_iters = nf > D ? (nf + D - 1) / D : 1;
+    fr[0] = ring_next();
+    ring_issue(fr[0], va);
+  } else {
+    if (mk) { fa = get_bond(next_lane(mk)); issue(fa, va); have_a = true; }
+  }
 
   // ---- diagonal (needs own) ----
   V acc[R];
@@ -277,20 +327,44 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   // point here, their own rows have just arrived), so that afterwards every wave runs its stream and suffix phases on
   // its own clock and one wave's LDS/VALU phase overlaps its neighbours' memory phase.
   __syncthreads();
-  // ---- 3. far bonds: ping-pong pipeline, accumulation in bond order ----
-  // (The issues are conditional, so the compiler cannot count the loads in flight and drains them all before each
+  // ---- 3. far bonds: ping-pong pipeline (PACK: the ring), accumulation in bond order ----
+  // (Ping-pong: the issues are conditional, so the compiler cannot count the loads in flight and drains them all before each
   // accumulation: the two register sets overlap less than the source suggests.  Three rewrites with counted waits -- loads
-  // always issued, EMPTY bonds at the end -- were measured and lose or tie: profiles/ablation_r03.md section 3.)
-  while (have_a) {
-    bool have_b = false;
-    if (mk) { fbb = get_bond(next_lane(mk)); issue(fbb, vb); have_b = true; }
+  // always issued, EMPTY bonds at the end -- were measured and lose or tie for the class launches: profiles/ablation_r03.md
+  // section 3.  The packed form takes the first of them, see SD_PACK_RING above.)
+  if constexpr (PACK) {
+    // the first iteration (its entry 0 is in flight since before the barrier), then whole iterations: issue D, accumulate D
 #pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fa.J, va[r]);
-    have_a = false;
-    if (!have_b) break;
-    if (mk) { fa = get_bond(next_lane(mk)); issue(fa, va); have_a = true; }
+    for (int k = 1; k < D; ++k) { fr[k] = ring_next(); ring_issue(fr[k], k == 1 ? vb : vx[k > 2 ? k - 2 : 0]); }
 #pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fbb.J, vb[r]);
+    for (int k = 0; k < D; ++k) {
+      V(&v)[R] = k == 0 ? va : k == 1 ? vb : vx[k > 2 ? k - 2 : 0];
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fr[k].J, v[r]);
+    }
+#pragma nounroll
+    for (int it = 1; it < ring_iters; ++it) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) { fr[k] = ring_next(); ring_issue(fr[k], k == 0 ? va : k == 1 ? vb : vx[k > 2 ? k - 2 : 0]); }
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        V(&v)[R] = k == 0 ? va : k == 1 ? vb : vx[k > 2 ? k - 2 : 0];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fr[k].J, v[r]);
+      }
+    }
+  } else {
+    while (have_a) {
+      bool have_b = false;
+      if (mk) { fbb = get_bond(next_lane(mk)); issue(fbb, vb); have_b = true; }
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fa.J, va[r]);
+      have_a = false;
+      if (!have_b) break;
+      if (mk) { fa = get_bond(next_lane(mk)); issue(fa, va); have_a = true; }
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fbb.J, vb[r]);
+    }
   }
   // The packed partner table of the suffix bonds is requested only now: its 4 registers per row would otherwise be live
   // across the stream phase and cost a wave per SIMD (89 instead of 74 VGPRs for ComplexF64).  An L2 / L1 hit.
@@ -1070,7 +1144,11 @@ int sd_launch_apply(sd_ctx *ctx, const sd_model *m, int dtype, void *out, const 
       // PACK); four images of 1 + 256 rows and the reduction scratch.  Then the short tiles and the reduction as always.
       const bool packed = part == 0 && dtype == SD_C128 && dm.n_blk > 0;
       if (packed) {
-        const size_t shmem = (size_t)4 * 257 * esz + 32 * sizeof(double) + 16;
+        // SD_PACK_WGS_PER_CU < 6: the request is padded to the middle between a CU's 160 KiB over the cap and over the cap + 1, so
+        // that the cap holds whatever the allocation granule (the kernel uses the first 16 720 bytes only)
+        constexpr size_t LDS_CU = 160 * 1024, WGS = SD_PACK_WGS_PER_CU;
+        const size_t need = (size_t)4 * 257 * esz + 32 * sizeof(double) + 16;
+        const size_t shmem = WGS >= 6 ? need : std::max(need, ((LDS_CU / WGS + LDS_CU / (WGS + 1)) / 2) & ~(size_t)255);
         rc = m->hop_pow2 ? launch_tiled_cfg<2, 4, 256, true, true, false, true>(ctx, dm, dm.n_blk, shmem, (double *)out, (const double *)psi, epi, ea, 1024)
                          : launch_tiled_cfg<2, 4, 256, false, true, false, true>(ctx, dm, dm.n_blk, shmem, (double *)out, (const double *)psi, epi, ea, 1024);
       }
