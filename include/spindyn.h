@@ -391,6 +391,31 @@ int sd_structure_factor_dev(sd_ctx *ctx, const sd_model *m, int dtype, const voi
 #define SD_PAIR_PM 1
 int sd_pair_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int component, double *M_out);
 int sd_pair_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int component, double *M_out);
+/* Bond operators and dimer correlations of one state (sites 1-based; nothing is divided by <psi|psi>).  For a bond b = (i, j), i != j,
+ * and two real weights
+ *   D_b = xy/2 (S^+_i S^-_j + S^-_i S^+_j) + zz S^z_i S^z_j          (xy = zz = 1: S_i . S_j; symmetric in i, j):
+ *   (D_b psi)(s) = +-(zz/4) psi(s), + when the two sites agree in s, plus (xy/2) psi(s') when they differ, s' = s with the two sites
+ *   exchanged.  D_b conserves S^z: fixed-nup sectors and the full basis alike.
+ * sd_bond_apply: out (n elements of psi's dtype) = D_b psi, every row written.  _dev: device pointers, out_dev must not alias
+ *   psi_dev (SD_EARG).
+ * sd_dimer_correlations: for the B bonds (i_0, j_0, i_1, j_1, ...) of `bonds` (2 B host ints; a bond may appear twice or reversed),
+ *   D_out: 2 B B host doubles, (re, im) of D[a][b] = <psi| D_a D_b |psi> = sum_s conj((D_a psi)(s)) (D_b psi)(s) row-major, both
+ *          triangles and the diagonal.  Hermitian to the bit (one triangle is summed), the diagonal's imaginary parts exactly 0;
+ *          complex for a ComplexF64 psi when bonds overlap (D_a and D_b do not commute then), imaginary parts exactly 0 for a Float64 psi.
+ *   e_out: B host doubles, e[b] = <psi| D_b |psi>.
+ *   One pass of a Gram-accumulating gather kernel: no vector D_b psi is stored.  Sums in a fixed order: the same call gives the
+ *   same bits.  _dev: psi is a device pointer; the call synchronises the stream.
+ * SD_EARG: i == j, a site outside 1..L, B < 1 or B > SD_DIMER_MAX_BONDS, a dtype other than SD_F64 / SD_C128, weights that are not
+ * finite, a sharded model, a model without device tables.  SD_EDIM: n is not the basis dimension.  A model with no rows gives zeros. */
+#define SD_DIMER_MAX_BONDS 128
+int sd_bond_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int i, int j, double xy, double zz,
+                  void *out_host);
+int sd_bond_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int i, int j, double xy, double zz,
+                      void *out_dev);
+int sd_dimer_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *bonds, int B,
+                          double xy, double zz, double *D_out, double *e_out);
+int sd_dimer_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *bonds, int B,
+                              double xy, double zz, double *D_out, double *e_out);
 /* create_spin_operator(site, op)(psi, model)   src/Hamiltonian.jl:49-136.  site is 1-based.  S^z is diagonal and works
  * in any basis; S^+, S^-, S^x, S^y change the magnetisation and are rejected in a fixed-nup sector (SD_EARG), as the
  * reference does.  out has psi's element type; S^y needs a ComplexF64 psi (SD_EARG otherwise: the reference's

@@ -21,7 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
-       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, pair_correlations, typicality_sample, typicality_correlation_function,
+       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, pair_correlations, bond_operator, dimer_correlations, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -505,6 +505,44 @@ function pair_correlations(psi::AbstractVector, model::Model; component::Symbol=
     check(ccall((:sd_pair_correlations, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint, Ptr{Float64}),
                 model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), component === :pm ? 1 : 0, out), model.ctx.h)
     return permutedims(reshape(reinterpret(ComplexF64, out), model.L, model.L))     # the ABI is row-major
+end
+
+# bonds: a vector of (i, j) site pairs (1-based, i != j), or nothing for the distinct site pairs of the model's hopping list in list order
+function bond_list(model::Model, bonds)
+    bonds === nothing || return [(Int(b[1]), Int(b[2])) for b in bonds]
+    seen = Set{Tuple{Int,Int}}(); out = Tuple{Int,Int}[]
+    for h in model.hopping_list
+        key = (min(h[1], h[2]), max(h[1], h[2]))
+        if h[1] != h[2] && !(key in seen)
+            push!(seen, key); push!(out, (Int(h[1]), Int(h[2])))
+        end
+    end
+    return out
+end
+
+# D_b psi for the bond b = (i, j): D_b = xy/2 (S^+_i S^-_j + S^-_i S^+_j) + zz S^z_i S^z_j (xy = zz = 1: S_i . S_j)  (DESIGN.md 16)
+function bond_operator(psi::AbstractVector, model::Model, i::Integer, j::Integer; xy::Real=1.0, zz::Real=1.0)
+    p = hostvec(psi)
+    out = similar(p)
+    check(ccall((:sd_bond_apply, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint, Cint, Float64, Float64, Ptr{Cvoid}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), i, j, Float64(xy), Float64(zz), out), model.ctx.h)
+    return out
+end
+
+# Dimer correlations of psi for a list of B bonds from one pass: (D, e), D[a, b] = <psi| D_a D_b |psi> (B x B ComplexF64, Hermitian),
+# e[b] = <psi| D_b |psi>; nothing divided by <psi|psi>
+function dimer_correlations(psi::AbstractVector, model::Model; bonds=nothing, xy::Real=1.0, zz::Real=1.0)
+    bl = bond_list(model, bonds)
+    B = length(bl)
+    flat = Cint[x for b in bl for x in b]
+    p = hostvec(psi)
+    D = Vector{Float64}(undef, 2 * B * B)
+    e = Vector{Float64}(undef, B)
+    check(ccall((:sd_dimer_correlations, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cint}, Cint, Float64, Float64, Ptr{Float64}, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), flat, B, Float64(xy), Float64(zz), D, e), model.ctx.h)
+    return permutedims(reshape(reinterpret(ComplexF64, D), B, B)), e     # the ABI is row-major
 end
 
 # operator descriptors: (:Sz, site), (:Szq, q), :Sz_all (operator_i only), (:current, weights | nothing) -> (kind, parameter, weights)

@@ -18,7 +18,8 @@ from .solvers import (chebyshev_coeffs, chebyshev_time_evolve, compute_chebyshev
                       kpm_correlation_matrix, kpm_reconstruct_signed, kpm_site_moments, kpm_sqw_sites, site_project)
 from .typicality import (chebyshev_imag_coeffs, current_expectation, dqt_sample, spin_current, thermal_energy, thermal_state,
                          typicality_correlation_function)
-from .observables import (connected_correlations, correlation_matrix, magnetization_per_site, momentum_distribution,
+from .observables import (bond_energies, bond_operator, connected_correlations, correlation_matrix, dimer_correlation_matrix,
+                          dimer_structure_factor, magnetization_per_site, model_bonds, momentum_distribution,
                           static_structure_factor, structure_factor_Sq)
 from . import initial_states
 from .initial_states import domain_wall_state, neel_state, polarized_state, polarized_state_with_flips

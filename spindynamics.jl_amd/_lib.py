@@ -150,6 +150,10 @@ PROTOTYPES = {
     "sd_current_bracket_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _dp, _dp]),
     "sd_pair_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _i, _dp]),
     "sd_pair_correlations_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _dp]),
+    "sd_bond_apply": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
+    "sd_bond_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
+    "sd_dimer_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _d, _d, _dp, _dp]),
+    "sd_dimer_correlations_dev": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _d, _d, _dp, _dp]),
     "sd_dqt_correlations": (_i, [_vp, _vp, _d, _vp, _u64, _i, _d, _dp, _i, _d, _dp, _dp, _i, _i, _i, _i, _d, _d, _dp, _dp, _dp, _dp]),
     "sd_magnetization": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),
     "sd_magnetization_dev": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),

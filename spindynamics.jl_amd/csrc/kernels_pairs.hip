@@ -10,11 +10,8 @@
 // (sector plans without tiles), 2 the row index (full basis).  Partner row s':
 //   MODE 2: idx ^ mask.
 //   MODE 1: the plan's own rank, idx0(s') = addr[prefix of s'] + suf_rank[suffix of s'] (sd_internal.hpp), two cached loads.
-//   MODE 0: a LOCAL rank difference.  Moving one up spin from bj down to bi leaves r_k (the ups still to place at site k) as it is
-//           below bi and above bj and lowers it by one in between, so only the terms of sites bi..bj of rank_g's sum change:
-//             idx(s) - idx(s') = C(L-1-bi, r-1) + sum_{bi<b<bj, b down} [C(L-1-b, r_b-1) - C(L-1-b, r_b-2)] - C(L-1-bj, r_bj-2),
-//           C(n, -1) = 0, r = nup - popcount(s below bi).  O(bj - bi) lookups instead of O(L), the binomials in LDS as in
-//           k_current; for neighbours the walk is empty and the two end terms are k_current's closed form by Pascal's rule.
+//   MODE 0: a LOCAL rank difference, O(bj - bi) lookups instead of O(L), the binomials in LDS as in k_current; for neighbours the
+//           walk is empty and the two end terms are k_current's closed form by Pascal's rule (pair_partner, device_common.hpp).
 // Sums: per thread, block_reduce2 per pair, block partials in ctx->d_partials, k_pairs_reduce adds them in a fixed order.  No
 // atomics, and the grid depends on the plan alone: the same call gives the same bits.
 #include <hip/hip_runtime.h>
@@ -30,27 +27,6 @@ namespace {
 #define SD_PAIR_CHUNK 8          // pairs per workgroup column
 #define SD_PAIR_ROW (2 * SD_PAIR_CHUNK)   // doubles of a block's partial row
 #define SD_PAIR_MAX_BLOCKS 2048  // row blocks (grid.y): tiles of a tiled plan, else blocks of 256 rows, capped here
-
-template <int MODE>
-__device__ __forceinline__ int64_t pair_partner(const sd_dev_model &dm, const int64_t *lbin, int K, uint64_t s, int64_t idx, int bi,
-                                                int bj) {
-  const uint64_t mask = ((uint64_t)1 << bi) | ((uint64_t)1 << bj);
-  if (MODE == 2) return idx ^ (int64_t)mask;
-  if (MODE == 1) {
-    const uint64_t t = s ^ mask;
-    return dm.addr[(uint32_t)t & (((uint32_t)1 << dm.p) - 1u)] + (int64_t)dm.suf_rank[t >> dm.p];
-  }
-  int r = dm.nup - __popcll(s & (((uint64_t)1 << bi) - 1));     // >= 1: site bj is still to come
-  int64_t d = lbin[(dm.L - 1 - bi) * K + r - 1];
-  for (int b = bi + 1; b < bj; ++b) {
-    if ((s >> b) & 1) { --r; continue; }
-    const int64_t *row = lbin + (dm.L - 1 - b) * K;
-    d += row[r - 1];
-    if (r >= 2) d -= row[r - 2];
-  }
-  if (r >= 2) d -= lbin[(dm.L - 1 - bj) * K + r - 2];
-  return idx - d;
-}
 
 // NC: components of psi.  pairs[k] = bi | bj << 8 (0-based bits, bi <= bj).  PM false: the ZZ form (sums before the factor 1/4).
 template <int NC, bool PM, int MODE>

@@ -1828,6 +1828,83 @@ int pair_correlations_core(sd_ctx *ctx, const sd_model *m, int dtype, const void
   return SD_OK;
 }
 
+// the 0-based bits lo < hi of the bond of the 1-based sites (i, j): D_b is symmetric in its two sites
+int bond_bits(sd_ctx *ctx, const sd_model *m, int i, int j, int *lo, int *hi) {
+  if (i < 1 || i > m->L || j < 1 || j > m->L) return sd_set_err(ctx, SD_EARG, "a bond site is outside 1..L");
+  if (i == j) return sd_set_err(ctx, SD_EARG, "the two sites of a bond must differ");
+  *lo = std::min(i, j) - 1; *hi = std::max(i, j) - 1;
+  return SD_OK;
+}
+
+// out (n elements of psi's dtype) = D_b psi, b = (i, j)
+int bond_apply_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int i, int j, double xy, double zz, void *out,
+                    bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  int lo = 0, hi = 0;
+  RC(bond_bits(ctx, m, i, j, &lo, &hi));
+  if (!std::isfinite(xy) || !std::isfinite(zz)) return sd_set_err(ctx, SD_EARG, "the bond weights must be finite");
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!out) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (on_dev && out == psi) return sd_set_err(ctx, SD_EARG, "out must not alias psi");
+  DBuf in, res;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  double *o = (double *)out;
+  if (!on_dev) { RC(res.alloc(ctx, nc * n)); o = res.p; }
+  RC(sd_launch_bond_apply(ctx, m, dtype, p, lo, hi, xy, zz, o));
+  if (!on_dev) return d2h(ctx, out, o, nc * n);
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+
+// D_out (host, 2 B B doubles) = the B x B dimer matrix of psi, e_out (host, B doubles) the bond expectation values: the kernel sums
+// the tiles of the upper triangle of 4-bond chunks (inside a diagonal tile a <= b is used), the other triangle is the conjugate
+int dimer_correlations_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const int *bonds, int B, double xy,
+                            double zz, double *D_out, double *e_out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  if (B < 1 || B > SD_DIMER_MAX_BONDS) return sd_set_err(ctx, SD_EARG, "the number of bonds must be in 1..SD_DIMER_MAX_BONDS");
+  if (!bonds || !D_out || !e_out) return sd_set_err(ctx, SD_EARG, "null argument");
+  std::vector<int> packed((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    int lo = 0, hi = 0;
+    RC(bond_bits(ctx, m, bonds[2 * b], bonds[2 * b + 1], &lo, &hi));
+    packed[(size_t)b] = lo | (hi << 8);
+  }
+  if (!std::isfinite(xy) || !std::isfinite(zz)) return sd_set_err(ctx, SD_EARG, "the bond weights must be finite");
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  DBuf in, blist, res;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
+  RC(blist.alloc(ctx, (B + 1) / 2));
+  RC(sd_xfer_h2d(ctx, blist.p, packed.data(), sizeof(int) * (size_t)B));
+  const int ntiles = sd_dimer_tiles(B), nch = (B + 3) / 4;
+  RC(res.alloc(ctx, (int64_t)ntiles * SD_DIMER_TILE_ROW));
+  RC(sd_launch_dimer_gram(ctx, m, dtype, p, (const int *)blist.p, B, xy, zz, res.p));
+  std::vector<double> h((size_t)ntiles * SD_DIMER_TILE_ROW);
+  SD_HIP(ctx, hipMemcpyAsync(h.data(), res.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  size_t t = 0;
+  for (int ca = 0; ca < nch; ++ca)
+    for (int cb = ca; cb < nch; ++cb, ++t) {
+      const double *row = h.data() + t * SD_DIMER_TILE_ROW;
+      for (int ka = 0; ka < 4 && 4 * ca + ka < B; ++ka) {
+        const int a = 4 * ca + ka;
+        if (ca == cb) e_out[a] = row[32 + ka];
+        for (int kb = (ca == cb ? ka : 0); kb < 4 && 4 * cb + kb < B; ++kb) {
+          const int b = 4 * cb + kb;
+          const double re = row[2 * (4 * ka + kb)], im = row[2 * (4 * ka + kb) + 1];
+          double *up = D_out + 2 * ((size_t)a * B + b), *dn = D_out + 2 * ((size_t)b * B + a);
+          dn[0] = re; dn[1] = im == 0.0 ? 0.0 : -im;
+          up[0] = re; up[1] = im;
+        }
+      }
+    }
+  return SD_OK;
+}
+
 // an operator of the typicality driver: kind, site or momentum, device weights of a current
 struct DqtOp {
   int kind = 0; int site = 0; double q = 0.0; DBuf wt;
@@ -1902,6 +1979,23 @@ extern "C" int sd_pair_correlations(sd_ctx *ctx, const sd_model *m, int dtype, c
 extern "C" int sd_pair_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int component,
                                         double *M_out) {
   return abi_guard(ctx, [&]() -> int { return pair_correlations_core(ctx, m, dtype, psi_dev, n, component, M_out, true); });
+}
+
+extern "C" int sd_bond_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int i, int j, double xy,
+                             double zz, void *out_host) {
+  return abi_guard(ctx, [&]() -> int { return bond_apply_core(ctx, m, dtype, psi_host, n, i, j, xy, zz, out_host, false); });
+}
+extern "C" int sd_bond_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int i, int j, double xy,
+                                 double zz, void *out_dev) {
+  return abi_guard(ctx, [&]() -> int { return bond_apply_core(ctx, m, dtype, psi_dev, n, i, j, xy, zz, out_dev, true); });
+}
+extern "C" int sd_dimer_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *bonds,
+                                     int B, double xy, double zz, double *D_out, double *e_out) {
+  return abi_guard(ctx, [&]() -> int { return dimer_correlations_core(ctx, m, dtype, psi_host, n, bonds, B, xy, zz, D_out, e_out, false); });
+}
+extern "C" int sd_dimer_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *bonds,
+                                         int B, double xy, double zz, double *D_out, double *e_out) {
+  return abi_guard(ctx, [&]() -> int { return dimer_correlations_core(ctx, m, dtype, psi_dev, n, bonds, B, xy, zz, D_out, e_out, true); });
 }
 
 extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, const void *r_host, uint64_t seed, int B_kind,

@@ -299,6 +299,19 @@ int sd_launch_current(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec
 int sd_launch_pair_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int component, const int *pairs_dev,
                                 int npairs, double *dst);
 
+// Bond operators and dimer correlations (kernels_dimer.hip): D_b = xy/2 (S^+_i S^-_j + S^-_i S^+_j) + zz S^z_i S^z_j for the bond of
+// the 0-based bits bi < bj < L.  Unsharded models; queued on the context's stream, deterministic.
+// out (device, psi's dtype, every row written; must not alias psi) = D_b psi
+int sd_launch_bond_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int bi, int bj, double xy, double zz, void *out);
+// The bonds of a list are cut into chunks of 4; tile (ca, cb), ca <= cb, of the upper triangle of chunks (counted row by row,
+// sd_dimer_tiles(B) of them) has one row of SD_DIMER_TILE_ROW doubles in dst (device): (re, im) of D_ab = <psi|D_a D_b|psi> at
+// [2 (4 a + b)] for bond a of chunk ca and bond b of chunk cb, then -- diagonal tiles only -- e_a = <psi|D_a|psi> at [32 + a].  Entries of
+// bonds past the list are 0.  bonds_dev: B device ints bi | bj << 8.  Nothing is divided by <psi|psi>.
+#define SD_DIMER_TILE_ROW 36
+int sd_dimer_tiles(int B);
+int sd_launch_dimer_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, const int *bonds_dev, int B, double xy, double zz,
+                         double *dst);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.
