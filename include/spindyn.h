@@ -353,6 +353,8 @@ int sd_current_bracket_dev(sd_ctx *ctx, const sd_model *m, int dtype_bra, const 
 #define SD_DQT_SZ_Q 1      /* S^z_q of sd_szq; as the measured operator A its adjoint: <S^z_q psi| phi> */
 #define SD_DQT_SZ_ALL 2    /* A only: S^z_i for every site i = 1..L at once (nA = L) */
 #define SD_DQT_CURRENT 3   /* J_w of the model's hop list (also with a caller's operator) */
+#define SD_DQT_ENERGY_CURRENT 4   /* J_E of the model's lists (sd_energy_current_terms, below), as A and as B; `param` is the geometry,
+                                     0 a line, 1 a ring; `w` must be NULL (SD_EARG).  The list is built once per call. */
 /* One sample of <A(t) B>_beta.  r_host: the start vector (ComplexF64, n = sd_model_dim elements) or NULL for the counter-based
  * normal stream of `seed` (sd_fill_randn_host(x, 2n, seed, 0) gives the same vector on the host); it is normalised first.
  * beta >= 0 (0 skips the imaginary-time step); times[nt] non-decreasing, times[0] >= 0.  method / cheb_n / kry_m / Emin / Emax as
@@ -366,6 +368,42 @@ int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, const void 
                         double B_param, const double *w_B, int A_kind, double A_param, const double *w_A, const double *times,
                         int nt, int method, int cheb_n, int kry_m, double Emin, double Emax, double *num_out, double *den_out,
                         double *energy_out, double *log_norm);
+
+/* ---- energy current: lists of dressed bond currents -------------------------------------------------------------------
+ * With the unit bond current j'_ij = i (S^+_i S^-_j - S^-_i S^+_j) a TERM (i, j, k, c) stands for c S^z_k j'_ij; i != j and k not in
+ * {i, j}, or k = 0: no S^z factor.  Sites are 1-based.  A list J = sum of its terms is Hermitian and conserves S^z (fixed-nup sectors
+ * and the full basis alike).  Consecutive terms with the same ordered (i, j) form a GROUP.  Row form, as computed (no fused
+ * multiply-add):
+ *   (J psi)[s] = i * sum_groups [s_i != s_j] (sigma co) psi[s with sites i, j exchanged],  sigma = +1 when site i is up in s,
+ *   co = sum over the group's terms, in list order from 0.0, of (k == 0 ? c : (site k up in s ? 0.5 c : -0.5 c)),
+ * real and imaginary parts summed separately in group order from zero, the factor i as the exact swap (re, im) -> (-im, re); one
+ * gather per group.
+ *
+ * sd_energy_current_terms: the energy current of the model's lists as such a list (host only; works on a model created without
+ *   a context).  H = sum_a h_a with hops t (S^+_i S^-_j + h.c.), zz terms v S^z_i S^z_j and field terms B_i S^z_i; a bond (i, j) sits
+ *   at x = i + delta/2, delta = j - i, a field term at x = i; with periodic = 1, delta and every position difference are minimum
+ *   images on a ring of L sites.  J_E = (i/2) sum_{a,b} (x_b - x_a) [h_a, h_b]; on a line this is i [H, sum_a x_a h_a].  Terms of
+ *   equal (i, j, k) are merged after orienting each to i < j (swapping i and j flips the sign of c), exact zeros dropped, the list
+ *   sorted by (i, j, k): that order is part of the interface.  cap = 0: only *n_terms is set.  SD_EARG: a position difference of
+ *   exactly +-L/2 with periodic = 1, more than SD_DTERM_MAX terms, 0 < cap < *n_terms, periodic not 0 or 1.
+ * sd_dcurrent_apply: out (ComplexF64, n elements) = J psi for an explicit list (a subset of the above: a local energy current; or a
+ *   caller's own), psi of `dtype`.  _dev: device pointers, out_dev must not alias psi_dev.
+ * sd_dcurrent_bracket: out[0..1] (host) = (re, im) of <bra| J |ket> without writing J ket; bra of `dtype_bra`, ket ComplexF64; sums
+ *   in a fixed order, the same call gives the same bits.
+ * SD_EARG: i == j, k in {i, j}, a site outside 1..L (k may also be 0), a coefficient that is not finite, n_terms outside
+ * 0..SD_DTERM_MAX, out aliasing psi, a sharded model, a model without device tables, another dtype.  SD_EDIM: n is not the basis
+ * dimension.  An empty list or a model with no rows gives a zero vector / a zero bracket. */
+#define SD_DTERM_MAX 4096
+typedef struct sd_dterm { int32_t i, j, k; double c; } sd_dterm;
+int sd_energy_current_terms(const sd_model *m, int periodic, sd_dterm *out, int cap, int *n_terms);
+int sd_dcurrent_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_dterm *terms, int n_terms,
+                      void *out_c128_host);
+int sd_dcurrent_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_dterm *terms, int n_terms,
+                          void *out_c128_dev);
+int sd_dcurrent_bracket(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_host, const void *ket_c128_host, int64_t n,
+                        const sd_dterm *terms, int n_terms, double *out);
+int sd_dcurrent_bracket_dev(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_dev, const void *ket_c128_dev, int64_t n,
+                            const sd_dterm *terms, int n_terms, double *out);
 
 /* ---- observables and initial states (reference src/Observables.jl, src/InitialStates.jl) ---- */
 /* magnetization_per_site   src/Observables.jl:14-36 : mags_out[L] = <S^z_i> */

@@ -21,7 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
-       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, pair_correlations, bond_operator, dimer_correlations, typicality_sample, typicality_correlation_function,
+       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -496,6 +496,52 @@ function current_expectation(bra::AbstractVector, ket::AbstractVector, model::Mo
     return complex(out[1], out[2])
 end
 
+# ---- energy current: lists of dressed bond currents (DESIGN.md 17) ----
+# sd_dterm: the term c S^z_k j'_ij, j'_ij = i (S⁺_i S⁻_j - S⁻_i S⁺_j); k = 0: no S^z factor
+struct DTerm
+    i::Int32
+    j::Int32
+    k::Int32
+    c::Float64
+end
+
+# The energy current J_E of the model's lists as a list of terms, sorted by (i, j, k); boundary :periodic: positions on a ring
+function energy_current_terms(model::Model; boundary::Symbol=:open)
+    boundary in (:open, :periodic) || throw(ArgumentError("boundary must be :open or :periodic"))
+    per = boundary === :periodic ? 1 : 0
+    n = Ref{Cint}(0)
+    check(ccall((:sd_energy_current_terms, libspindyn), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Cint}),
+                model.h, per, C_NULL, 0, n), model.ctx.h)
+    out = Vector{DTerm}(undef, n[])
+    n[] == 0 && return out
+    check(ccall((:sd_energy_current_terms, libspindyn), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Cint}),
+                model.h, per, out, length(out), n), model.ctx.h)
+    return out
+end
+
+dterm_list(model::Model, terms, boundary) = terms === nothing ? energy_current_terms(model; boundary=boundary) :
+    DTerm[DTerm(Int32(t[1]), Int32(t[2]), Int32(t[3]), Float64(t[4])) for t in terms]
+
+# J ψ for a list of terms (i, j, k, c); terms nothing: the model's energy current
+function energy_current(ψ::AbstractVector, model::Model; terms=nothing, boundary::Symbol=:open)
+    x = hostvec(ψ); tl = dterm_list(model, terms, boundary)
+    out = Vector{ComplexF64}(undef, length(x))
+    check(ccall((:sd_dcurrent_apply, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}),
+                model.ctx.h, model.h, dtype_code(eltype(x)), x, length(x), tl, length(tl), out), model.ctx.h)
+    return out
+end
+
+# <bra| J |ket> without forming J ket
+function energy_current_expectation(bra::AbstractVector, ket::AbstractVector, model::Model; terms=nothing, boundary::Symbol=:open)
+    b = hostvec(bra); k = Vector{ComplexF64}(ket); tl = dterm_list(model, terms, boundary)
+    length(b) == length(k) || throw(DimensionMismatch("length(bra) != length(ket)"))
+    out = Vector{Float64}(undef, 2)
+    check(ccall((:sd_dcurrent_bracket, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(b)), b, k, length(k), tl, length(tl), out), model.ctx.h)
+    return complex(out[1], out[2])
+end
+
 # Equal-time pair correlations of psi for all site pairs (DESIGN.md 15): component :pm gives <S^+_i S^-_j>, :zz gives <S^z_i S^z_j>;
 # L x L ComplexF64, nothing divided by <psi|psi>
 function pair_correlations(psi::AbstractVector, model::Model; component::Symbol=:zz)
@@ -545,13 +591,18 @@ function dimer_correlations(psi::AbstractVector, model::Model; bonds=nothing, xy
     return permutedims(reshape(reinterpret(ComplexF64, D), B, B)), e     # the ABI is row-major
 end
 
-# operator descriptors: (:Sz, site), (:Szq, q), :Sz_all (operator_i only), (:current, weights | nothing) -> (kind, parameter, weights)
+# operator descriptors: (:Sz, site), (:Szq, q), :Sz_all (operator_i only), (:current, weights | nothing),
+# (:energy_current, :open | :periodic) -> (kind, parameter, weights)
 function dqt_operator(model::Model, op)
     op === :Sz_all && return (2, 0.0, Ptr{Float64}(C_NULL))
     op isa Tuple && length(op) == 2 || throw(ArgumentError("unknown operator: $op"))
     op[1] === :Sz && return (0, Float64(op[2]), Ptr{Float64}(C_NULL))
     op[1] === :Szq && return (1, Float64(op[2]), Ptr{Float64}(C_NULL))
     op[1] === :current && return (3, 0.0, current_weights(model, op[2]))
+    if op[1] === :energy_current
+        op[2] in (:open, :periodic) || throw(ArgumentError("(:energy_current, boundary) takes :open or :periodic"))
+        return (4, op[2] === :periodic ? 1.0 : 0.0, Ptr{Float64}(C_NULL))
+    end
     throw(ArgumentError("unknown operator: $op"))
 end
 

@@ -16,8 +16,8 @@ from .solvers import (chebyshev_coeffs, chebyshev_time_evolve, compute_chebyshev
                       krylov_time_evolve, lanczos_extremal, lanczos_groundstate, lanczos_sqw, lanczos_sqw_transverse,
                       lanczos_tridiag, rescaling_from_bounds, spectral_from_tridiagonal, symtridiag_eig,
                       kpm_correlation_matrix, kpm_reconstruct_signed, kpm_site_moments, kpm_sqw_sites, site_project)
-from .typicality import (chebyshev_imag_coeffs, current_expectation, dqt_sample, spin_current, thermal_energy, thermal_state,
-                         typicality_correlation_function)
+from .typicality import (chebyshev_imag_coeffs, current_expectation, dqt_sample, energy_current, energy_current_expectation,
+                         energy_current_terms, spin_current, thermal_energy, thermal_state, typicality_correlation_function)
 from .observables import (bond_energies, bond_operator, connected_correlations, correlation_matrix, dimer_correlation_matrix,
                           dimer_structure_factor, magnetization_per_site, model_bonds, momentum_distribution,
                           static_structure_factor, structure_factor_Sq)

@@ -154,6 +154,11 @@ PROTOTYPES = {
     "sd_bond_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
     "sd_dimer_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _d, _d, _dp, _dp]),
     "sd_dimer_correlations_dev": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _d, _d, _dp, _dp]),
+    "sd_energy_current_terms": (_i, [_vp, _i, _vp, _i, _ip]),
+    "sd_dcurrent_apply": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _i, _vp]),
+    "sd_dcurrent_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _i, _vp]),
+    "sd_dcurrent_bracket": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, _i, _dp]),
+    "sd_dcurrent_bracket_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, _i, _dp]),
     "sd_dqt_correlations": (_i, [_vp, _vp, _d, _vp, _u64, _i, _d, _dp, _i, _d, _dp, _dp, _i, _i, _i, _i, _d, _d, _dp, _dp, _dp, _dp]),
     "sd_magnetization": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),
     "sd_magnetization_dev": (_i, [_vp, _vp, _i, _vp, _i64, _dp]),

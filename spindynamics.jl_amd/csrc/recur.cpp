@@ -1795,6 +1795,71 @@ int current_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, con
   return SD_OK;
 }
 
+// A caller's list of dressed bond currents (include/spindyn.h, sd_dterm) validated, cut into groups and put on the device: both
+// tables in one block from the context's pool, the dressed coefficients halved (exact).  n_groups == 0: the empty list.
+struct DList {
+  DBuf buf;
+  int n_groups = 0;
+  const sd_dgroup *groups = nullptr;
+  const sd_dterm_dev *terms = nullptr;
+  int init(sd_ctx *ctx, const sd_model *m, const sd_dterm *list, int n_terms) {
+    if (n_terms < 0 || n_terms > SD_DTERM_MAX) return sd_set_err(ctx, SD_EARG, "the number of terms must be in 0..SD_DTERM_MAX");
+    if (n_terms > 0 && !list) return sd_set_err(ctx, SD_EARG, "null argument");
+    std::vector<sd_dgroup> g;
+    std::vector<sd_dterm_dev> t((size_t)n_terms);
+    for (int n = 0; n < n_terms; ++n) {
+      const sd_dterm &T = list[n];
+      if (T.i < 1 || T.i > m->L || T.j < 1 || T.j > m->L || T.k < 0 || T.k > m->L) return sd_set_err(ctx, SD_EARG, "a site of a term is outside 1..L (k may also be 0)");
+      if (T.i == T.j) return sd_set_err(ctx, SD_EARG, "the two sites of a bond current must differ");
+      if (T.k == T.i || T.k == T.j) return sd_set_err(ctx, SD_EARG, "the S^z site of a term must not be one of its bond's sites");
+      if (!std::isfinite(T.c)) return sd_set_err(ctx, SD_EARG, "the coefficients must be finite");
+      if (n == 0 || T.i != list[n - 1].i || T.j != list[n - 1].j) {
+        const int lo = std::min(T.i, T.j) - 1, hi = std::max(T.i, T.j) - 1;
+        g.push_back(sd_dgroup{lo | (hi << 8) | ((T.i > T.j ? 1 : 0) << 16), n, 0, 0});
+      }
+      ++g.back().count;
+      t[(size_t)n] = sd_dterm_dev{T.k == 0 ? T.c : 0.5 * T.c, T.k - 1, 0};
+    }
+    n_groups = (int)g.size();
+    if (n_groups == 0) return SD_OK;
+    static_assert(sizeof(sd_dgroup) == 16 && sizeof(sd_dterm_dev) == 16, "table layout");
+    RC(buf.alloc(ctx, 2 * (int64_t)(g.size() + t.size())));
+    groups = (const sd_dgroup *)buf.p;
+    terms = (const sd_dterm_dev *)(buf.p + 2 * g.size());
+    RC(sd_xfer_h2d(ctx, buf.p, g.data(), sizeof(sd_dgroup) * g.size()));
+    return sd_xfer_h2d(ctx, buf.p + 2 * g.size(), t.data(), sizeof(sd_dterm_dev) * t.size());
+  }
+};
+
+// write form (bra == null): out (ComplexF64, n) = J vec; bracket form: out[0..1] (host) = <bra|J|vec>, vec ComplexF64
+int dcurrent_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, bool bracket, int64_t n,
+                  const sd_dterm *list, int n_terms, void *out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!out || !vec) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (!bracket && on_dev && out == vec) return sd_set_err(ctx, SD_EARG, "out must not alias psi");
+  DList dl;
+  RC(dl.init(ctx, m, list, n_terms));
+  DBuf vin, bin, res;
+  const double *v = nullptr, *b = nullptr;
+  RC(site_stage(ctx, bracket ? SD_C128 : dtype, vec, on_dev, n, vin, &v));
+  if (bracket) {
+    RC(site_stage(ctx, dtype, bra, on_dev, n, bin, &b));
+    RC(res.alloc(ctx, 2));
+    RC(sd_launch_dcurrent(ctx, m, dtype, v, b, dl.groups, dl.n_groups, dl.terms, nullptr, res.p));
+    SD_HIP(ctx, hipMemcpyAsync(out, res.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SD_OK;
+  }
+  double *o = (double *)out;
+  if (!on_dev) { RC(res.alloc(ctx, 2 * n)); o = res.p; }
+  RC(sd_launch_dcurrent(ctx, m, dtype, v, nullptr, dl.groups, dl.n_groups, dl.terms, o, nullptr));
+  if (!on_dev) return d2h(ctx, out, o, 2 * n);
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));        // the tables go back to the pool
+  return SD_OK;
+}
+
 // M_out (host, 2 L L doubles) = the L x L pair-correlation matrix of psi: the kernel sums the pairs i <= j, the other triangle is
 // the conjugate
 int pair_correlations_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int component, double *M_out,
@@ -1905,11 +1970,20 @@ int dimer_correlations_core(sd_ctx *ctx, const sd_model *m, int dtype, const voi
   return SD_OK;
 }
 
-// an operator of the typicality driver: kind, site or momentum, device weights of a current
+// an operator of the typicality driver: kind, site or momentum, device weights of a current, device tables of the energy current
 struct DqtOp {
-  int kind = 0; int site = 0; double q = 0.0; DBuf wt;
+  int kind = 0; int site = 0; double q = 0.0; DBuf wt; DList dl;
   int init(sd_ctx *ctx, const sd_model *m, int kind_, double param, const double *w, bool is_A) {
     kind = kind_;
+    if (kind == SD_DQT_ENERGY_CURRENT) {
+      if (w) return sd_set_err(ctx, SD_EARG, "the energy current takes no weights (w must be NULL)");
+      if (param != 0.0 && param != 1.0) return sd_set_err(ctx, SD_EARG, "the energy current's parameter is the geometry: 0 a line, 1 a ring");
+      std::vector<sd_dterm> list;
+      std::string err;
+      const int rc = sd_build_energy_current(m, param == 1.0, list, err);
+      if (rc) return sd_set_err(ctx, rc, err);
+      return dl.init(ctx, m, list.data(), (int)list.size());
+    }
     if (kind == SD_DQT_SZ_SITE) {
       site = (int)param;
       if ((double)site != param || site < 1 || site > m->L) return sd_set_err(ctx, SD_EARG, "site is outside 1..L");
@@ -1969,6 +2043,43 @@ extern "C" int sd_current_bracket_dev(sd_ctx *ctx, const sd_model *m, int dtype_
   return abi_guard(ctx, [&]() -> int {
     if (!bra_dev) return sd_set_err(ctx, SD_EARG, "null argument");
     return current_core(ctx, m, dtype_bra, ket_dev, bra_dev, true, n, w, out, true);
+  });
+}
+
+extern "C" int sd_energy_current_terms(const sd_model *m, int periodic, sd_dterm *out, int cap, int *n_terms) {
+  return abi_guard(nullptr, [&]() -> int {
+    if (!m || !n_terms || cap < 0 || (cap > 0 && !out) || (periodic != 0 && periodic != 1)) return SD_EARG;
+    std::vector<sd_dterm> list;
+    std::string err;
+    const int rc = sd_build_energy_current(m, periodic, list, err);
+    if (rc) return m->ctx ? sd_set_err(m->ctx, rc, err) : rc;
+    *n_terms = (int)list.size();
+    if (cap == 0) return SD_OK;
+    if ((size_t)cap < list.size()) return m->ctx ? sd_set_err(m->ctx, SD_EARG, "cap is smaller than the number of terms") : SD_EARG;
+    std::copy(list.begin(), list.end(), out);
+    return SD_OK;
+  });
+}
+extern "C" int sd_dcurrent_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_dterm *terms,
+                                 int n_terms, void *out_host) {
+  return abi_guard(ctx, [&]() -> int { return dcurrent_core(ctx, m, dtype, psi_host, nullptr, false, n, terms, n_terms, out_host, false); });
+}
+extern "C" int sd_dcurrent_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_dterm *terms,
+                                     int n_terms, void *out_dev) {
+  return abi_guard(ctx, [&]() -> int { return dcurrent_core(ctx, m, dtype, psi_dev, nullptr, false, n, terms, n_terms, out_dev, true); });
+}
+extern "C" int sd_dcurrent_bracket(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_host, const void *ket_host, int64_t n,
+                                   const sd_dterm *terms, int n_terms, double *out) {
+  return abi_guard(ctx, [&]() -> int {
+    if (!bra_host) return sd_set_err(ctx, SD_EARG, "null argument");
+    return dcurrent_core(ctx, m, dtype_bra, ket_host, bra_host, true, n, terms, n_terms, out, false);
+  });
+}
+extern "C" int sd_dcurrent_bracket_dev(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_dev, const void *ket_dev, int64_t n,
+                                       const sd_dterm *terms, int n_terms, double *out) {
+  return abi_guard(ctx, [&]() -> int {
+    if (!bra_dev) return sd_set_err(ctx, SD_EARG, "null argument");
+    return dcurrent_core(ctx, m, dtype_bra, ket_dev, bra_dev, true, n, terms, n_terms, out, true);
   });
 }
 
@@ -2048,6 +2159,7 @@ extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, 
   double *phi = S + 2 * n;
   if (B_kind == SD_DQT_SZ_SITE) RC(sd_launch_spin_op(ctx, m, SD_C128, Bo.site, SD_SPIN_Z, S, phi));
   else if (B_kind == SD_DQT_SZ_Q) RC(sd_launch_szq(ctx, m, SD_C128, S, Bo.q, phi));
+  else if (B_kind == SD_DQT_ENERGY_CURRENT) RC(sd_launch_dcurrent(ctx, m, SD_C128, S, nullptr, Bo.dl.groups, Bo.dl.n_groups, Bo.dl.terms, phi, nullptr));
   else RC(sd_launch_current(ctx, m, SD_C128, S, nullptr, Bo.wt.p, phi, nullptr));
   double nphi = 0.0;
   if (method == SD_EVOLVE_KRYLOV) { nphi = norm_dev(op, phi, 2 * n, &rc); RC(rc); }
@@ -2095,6 +2207,8 @@ extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, 
       RC(sd_k_dot_to(ctx, 2, tmp.p, ph, n, dst));
     } else if (A_kind == SD_DQT_SZ_ALL) {
       RC(sd_launch_site_project(ctx, m, SD_C128, psi, 0, ph, n, 1, dst, mrow));
+    } else if (A_kind == SD_DQT_ENERGY_CURRENT) {
+      RC(sd_launch_dcurrent(ctx, m, SD_C128, ph, psi, Ao.dl.groups, Ao.dl.n_groups, Ao.dl.terms, nullptr, dst));
     } else {
       RC(sd_launch_current(ctx, m, SD_C128, ph, psi, Ao.wt.p, nullptr, dst));
     }

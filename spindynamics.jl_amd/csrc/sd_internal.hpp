@@ -293,6 +293,27 @@ int sd_launch_site_project(sd_ctx *ctx, const sd_model *m, int dtype_bra, const 
 int sd_launch_current(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, const double *wt_dev, void *out,
                       double *dst);
 
+// Lists of dressed bond currents c S^z_k j'_ij, the form of the energy current (kernels_ecurrent.hip).  Device tables
+// of a validated list: one sd_dgroup per run of consecutive terms with the same ordered (i, j), one sd_dterm_dev per term.
+struct sd_dgroup {
+  int32_t bits;      // lo | hi << 8 | (site i is the higher one) << 16: 0-based bits lo < hi of the pair
+  int32_t first;     // the group's terms: terms[first .. first + count)
+  int32_t count;
+  int32_t pad;
+};
+struct sd_dterm_dev {
+  double ch;         // c for k == 0, else 0.5 c (exact)
+  int32_t kb;        // 0-based bit of site k, -1: no S^z factor
+  int32_t pad;
+};
+// out != null: out (ComplexF64) = J vec, vec of `dtype`; out == null: dst[0..1] (device) = <bra|J|vec> with bra of `dtype` and vec
+// ComplexF64, nothing written.  Unsharded models; queued on the context's stream, deterministic.
+int sd_launch_dcurrent(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, const sd_dgroup *groups_dev,
+                       int n_groups, const sd_dterm_dev *terms_dev, void *out, double *dst);
+// The energy current of the model's lists as such a list (ecurrent_terms.cpp; host only): merged, oriented i < j, sorted by
+// (i, j, k).  SD_EARG with a message in `err` for an ambiguous minimum image or more than SD_DTERM_MAX terms.
+int sd_build_energy_current(const sd_model *m, int periodic, std::vector<sd_dterm> &out, std::string &err);
+
 // Equal-time pair correlations (kernels_pairs.hip): dst[2k .. +1] (device) = (re, im) of <psi|S^+_i S^-_j|psi> (SD_PAIR_PM) or
 // (<psi|S^z_i S^z_j|psi>, 0) (SD_PAIR_ZZ) for pair k of pairs_dev -- npairs device ints bi | bj << 8, 0-based bits, bi <= bj < L -- of
 // psi (`dtype`, device).  Nothing is divided by <psi|psi>.  Unsharded models; queued on the context's stream, deterministic.

@@ -20,7 +20,10 @@ from .model import Model
 from .solvers import _c128, _vec
 
 _dp = C.POINTER(C.c_double)
-_KINDS = {"Sz": 0, "Szq": 1, "Sz_all": 2, "current": 3}
+_KINDS = {"Sz": 0, "Szq": 1, "Sz_all": 2, "current": 3, "energy_current": 4}
+_BOUNDARY = {"open": 0, "periodic": 1}
+# sd_dterm (include/spindyn.h): the term c S^z_k j'_ij of a list of dressed bond currents
+DTERM = np.dtype([("i", np.int32), ("j", np.int32), ("k", np.int32), ("c", np.float64)], align=True)
 
 
 def chebyshev_imag_coeffs(a, tau, n_max=4096):
@@ -126,12 +129,91 @@ def current_expectation(bra, ket, model, weights=None):
     return complex(out[0], out[1])
 
 
+def _boundary(boundary):
+    if boundary not in _BOUNDARY:
+        raise ArgumentError("boundary must be \"open\" or \"periodic\"")
+    return _BOUNDARY[boundary]
+
+
+def energy_current_terms(model, boundary="open"):
+    """The energy current J_E = (i/2) sum_{a,b} (x_b - x_a) [h_a, h_b] of the model's lists as a list of terms c S^z_k j'_ij
+    (sd_energy_current_terms): a structured array with fields i, j, k, c, merged, oriented i < j and sorted by (i, j, k); k = 0
+    means no S^z factor.  boundary "periodic": positions are minimum images on a ring of L sites.  Host only: works on a model
+    built with ctx=None."""
+    per = _boundary(boundary)
+    ch = model.ctx.h if model.ctx is not None else None
+    n = C.c_int(0)
+    check(lib().sd_energy_current_terms(model.h, per, None, 0, C.byref(n)), ch)
+    out = np.zeros(n.value, dtype=DTERM)
+    if n.value:
+        check(lib().sd_energy_current_terms(model.h, per, out.ctypes.data, n.value, C.byref(n)), ch)
+    return out
+
+
+def _terms(model, terms, boundary):
+    if terms is None:
+        return energy_current_terms(model, boundary)
+    if isinstance(terms, np.ndarray) and terms.dtype == DTERM:
+        return np.ascontiguousarray(terms)
+    out = np.zeros(len(terms), dtype=DTERM)
+    for n, t in enumerate(terms):
+        if len(t) != 4:
+            raise ArgumentError("a term is (i, j, k, c)")
+        out[n] = (int(t[0]), int(t[1]), int(t[2]), float(t[3]))
+    return out
+
+
+def energy_current(psi, model, terms=None, boundary="open"):
+    """J psi for a list of terms (i, j, k, c) = c S^z_k i (S^+_i S^-_j - S^-_i S^+_j) -> ComplexF64; terms None: the model's energy
+    current energy_current_terms(model, boundary).  A subset of that list is a local energy current.  numpy arrays or torch
+    device tensors."""
+    tl = _terms(model, terms, boundary)
+    if _is_torch(psi):
+        import torch
+        code = _torch_code(model, psi)
+        out = torch.empty(len(psi), dtype=torch.complex128, device=psi.device)
+        check(lib().sd_dcurrent_apply_dev(model.ctx.h, model.h, code, psi.data_ptr(), len(psi), tl.ctypes.data, len(tl),
+                                          out.data_ptr()), model.ctx.h)
+        return out
+    x, code = _vec(psi)
+    out = np.empty(len(x), dtype=np.complex128)
+    check(lib().sd_dcurrent_apply(model.ctx.h, model.h, code, x.ctypes.data, len(x), tl.ctypes.data, len(tl), out.ctypes.data),
+          model.ctx.h)
+    return out
+
+
+def energy_current_expectation(bra, ket, model, terms=None, boundary="open"):
+    """<bra| J |ket> for the list of `energy_current` without forming J ket (fixed summation order: the same call gives the same
+    bits) -> complex.  bra Float64 or ComplexF64, ket ComplexF64; numpy arrays or torch device tensors (both of one kind)."""
+    tl = _terms(model, terms, boundary)
+    out = np.empty(2)
+    if _is_torch(bra) or _is_torch(ket):
+        import torch
+        if not (_is_torch(bra) and _is_torch(ket)):
+            raise ArgumentError("bra and ket must both be numpy arrays or both torch device tensors")
+        if ket.dtype != torch.complex128:
+            raise ArgumentError("ket must be complex128")
+        if len(bra) != len(ket):
+            raise DimensionMismatch("length(bra) != length(ket)")
+        code = _torch_code(model, bra)
+        _bind_torch_stream(model, ket)
+        check(lib().sd_dcurrent_bracket_dev(model.ctx.h, model.h, code, bra.data_ptr(), ket.data_ptr(), len(ket), tl.ctypes.data,
+                                            len(tl), out.ctypes.data_as(_dp)), model.ctx.h)
+        return complex(out[0], out[1])
+    b, code = _vec(bra)
+    k = _c128(ket, len(b), "ket")
+    check(lib().sd_dcurrent_bracket(model.ctx.h, model.h, code, b.ctypes.data, k.ctypes.data, len(k), tl.ctypes.data, len(tl),
+                                    out.ctypes.data_as(_dp)), model.ctx.h)
+    return complex(out[0], out[1])
+
+
 def _operator(model, op, is_A):
     """(kind, param, weights array or None, weights pointer) of an operator descriptor"""
     if isinstance(op, str):
         op = (op,)
     if not isinstance(op, (tuple, list)) or len(op) == 0 or op[0] not in _KINDS:
-        raise ArgumentError(f"unknown operator: {op!r}; expected (\"Sz\", site), (\"Szq\", q), \"Sz_all\" or (\"current\", weights)")
+        raise ArgumentError(f"unknown operator: {op!r}; expected (\"Sz\", site), (\"Szq\", q), \"Sz_all\", (\"current\", weights) "
+                            "or (\"energy_current\", boundary)")
     name = op[0]
     if name == "Sz_all":
         if not is_A or len(op) != 1:
@@ -140,6 +222,10 @@ def _operator(model, op, is_A):
     if name == "current":
         w, wp = _weights(model, op[1] if len(op) > 1 else None)
         return 3, 0.0, w, wp
+    if name == "energy_current":
+        if len(op) > 2:
+            raise ArgumentError("(\"energy_current\", boundary) takes one parameter")
+        return 4, float(_boundary(op[1] if len(op) > 1 else "open")), None, None
     if len(op) != 2:
         raise ArgumentError(f"operator {name!r} needs one parameter")
     if name == "Sz":
@@ -209,7 +295,8 @@ def typicality_correlation_function(model, beta, operator_i, operator_j, t_range
     list of start vectors / one vector) -> complex array (len(t_range),), or (len(t_range), L) for operator_i = "Sz_all", with
     per-sample `num`, `den`, `energy` and the standard error `stderr` attached (TypicalityResult).
 
-    Operators: ("Sz", site), ("Szq", q) (as operator_i: its adjoint), "Sz_all" (operator_i only), ("current", weights | None).
+    Operators: ("Sz", site), ("Szq", q) (as operator_i: its adjoint), "Sz_all" (operator_i only), ("current", weights | None),
+    ("energy_current", "open" | "periodic"): the model's energy current (energy_current_terms).
     method "chebyshev" or "krylov"; further keywords: cheb_n (0: automatic), kry_m, Ebounds.
 
     The model's basis is the trace: a sector model gives the canonical average at fixed S^z.  all_sectors=True sums the
