@@ -6,14 +6,23 @@ its own rows and, for every flippable prefix bond b (bits b-1, b differ), the wh
 bond half of tile P ^ (1 << (p-1)).  Blocks are dealt round-robin to 8 XCDs (block i -> XCD i % 8); an XCD keeps W tiles in
 flight; a tile's reads are spread evenly over its lifetime.  The L2 is modelled as a byte-capacity LRU over half-tiles.
 
-usage: python profiles/l2_model.py [L] [order ...]      orders: lex chunk orbit greedy ...
+usage: python profiles/l2_model.py [L] [order ...]      orders: lex chunk orbit greedy ... block<B>c<C>[d]
+  block<B>c<C>: block orbits (csrc/orbit_key.hpp through its restatement profiles/orbit_key.py) with the leading B four-site
+                blocks eligible and a capacity of C tenths of a bit; block0c60 is orbit6.  A trailing d deals every orbit to the
+                queue with the fewest rows so far instead of round-robin.  Rows per queue are printed for every orbit order.
+environment: LS, CAP_MIB, W (tiles in flight per XCD), LO / HI (tile lengths simulated; LO=1 HI=1024: the packed launch),
+  ASC=1 (tiles enumerated by ascending base row, the order in which sd_build_plan hands them to xcd_queues, instead of
+  ascending prefix integer), MALL_MIB.
+The packed launch at L=32 as the planner orders it, four workgroups (128 tiles) per CU in flight:
+  ASC=1 LO=1 HI=1024 W=128 python profiles/l2_model.py 32 orbit6 block2c78 block2c78d block5c72 block5c72d
 """
 import os
 import sys
 from collections import OrderedDict
 from math import comb
 
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from orbit_key import orbit_key  # noqa: E402
 
 L = int(sys.argv[1]) if len(sys.argv) > 1 else 28
 orders = sys.argv[2:] or ["lex", "chunk", "orbit"]
@@ -33,7 +42,21 @@ def n_up_first(P):     # rows whose first suffix site is up
     return comb(LS - 1, t - 1) if t >= 1 else 0
 
 
+def tile_base(P):      # base row of tile P in the basis order (site 1 most significant, up first): basis.cpp tile_base_global
+    idx, r = 0, nup
+    for k in range(1, p + 1):
+        if r <= 0:
+            break
+        if (P >> (k - 1)) & 1:
+            r -= 1
+        else:
+            idx += comb(L - k, r - 1)
+    return idx
+
+
 all_tiles = [P for P in range(1 << p) if LO <= tile_len(P) <= HI]
+if os.environ.get("ASC", "0") == "1":
+    all_tiles.sort(key=tile_base)
 
 
 def canon(P, FO, greedy):
@@ -50,10 +73,13 @@ def canon(P, FO, greedy):
     return C0, member
 
 
-def order_orbit(tiles, FO=6, greedy=False, OC=1, gray=False):
+def order_orbit(tiles, FO=6, greedy=False, OC=1, gray=False, block=None, deal_rows=False):
     first, keys = {}, []
     for P in tiles:
-        C0, mem = canon(P, FO, greedy)
+        if block:
+            C0, mem, _ = orbit_key(P, p, block[0], block[1])
+        else:
+            C0, mem = canon(P, FO, greedy)
         if C0 not in first:
             first[C0] = len(first)
         if gray:
@@ -61,14 +87,20 @@ def order_orbit(tiles, FO=6, greedy=False, OC=1, gray=False):
         keys.append((first[C0], mem))
     idx = sorted(range(len(tiles)), key=lambda k: keys[k])
     q = [[] for _ in range(8)]
-    o, k = 0, 0
+    rows = [0] * 8
+    o, k, largest = 0, 0, 0
     while k < len(idx):
         e = k
         while e < len(idx) and keys[idx[e]][0] == keys[idx[k]][0]:
             e += 1
-        q[(o // OC) % 8].extend(tiles[i] for i in idx[k:e])
+        x = rows.index(min(rows)) if deal_rows else (o // OC) % 8      # fewest rows so far, ties to the lowest queue index
+        q[x].extend(tiles[i] for i in idx[k:e])
+        rows[x] += sum(tile_len(tiles[i]) for i in idx[k:e])
+        largest = max(largest, e - k)
         o += 1
         k = e
+    print(f"  orbits {o}  largest {largest} tiles  rows per queue {rows}"
+          f"  max - min {(max(rows) - min(rows)) / (sum(rows) / 8) * 100:.3f} % of the mean")
     return q
 
 
@@ -160,6 +192,10 @@ def parse(name):
         return order_lex(all_tiles)
     if name.startswith("chunk"):
         return order_chunk(all_tiles, int(name[5:] or 32))
+    if name.startswith("block"):
+        deal = name.endswith("d")
+        B_, C_ = name[5:].rstrip("d").split("c")
+        return order_orbit(all_tiles, block=(int(B_), int(C_)), deal_rows=deal)
     if name.startswith("orbit") or name.startswith("greedy") or name.startswith("gray"):
         kind = "greedy" if name.startswith("greedy") else ("gray" if name.startswith("gray") else "orbit")
         rest = name[len(kind):]

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "orbit_key.hpp"
 #include "sd_internal.hpp"
 
 int64_t sd_binom(int n, int k) {
@@ -143,11 +144,32 @@ static int count_nn_hops(const sd_model *m) {
 // that XCD's L2 (or merge with the in-flight fetch) instead of going to the fabric again.  FO = max f; plans without
 // orbits (too few tiles, p < 3, no chain) deal runs of CH consecutive tiles to each XCD.  Speed only: a bijection of the tile list.
 // xcd_queues returns the eight queues (entries index tp); xcd_order interleaves them, position j of queue x -> block 8j + x.
-// FO: one XCD order per length class (xcd_order): 5 beats 6 by 1 % at L=28..32 (profiles/ablation_r02.md §14); all tile lengths in
-// one launch (the block table of sd_build_plan): 6 beats 5 by 2.4 %, L=32 ComplexF64 10.97 -> 10.71 ms (profiles/ablation_packed_launch.md).
-static const int XCD_FO_CLASSES = 5, XCD_FO_PACKED = 6;
+// Orbit rule (orbit_key.hpp): (quad_blocks, capacity in tenths of a bit).  One XCD order per length class (xcd_order): odd-pair
+// orbits of 2^5, 5 beats 6 by 1 % at L=28..32 (profiles/ablation_r02.md §14).  All tile lengths in one launch (the block table of
+// sd_build_plan): 2^6 beats 2^5 by 2.4 %, L=32 ComplexF64 10.97 -> 10.71 ms (profiles/ablation_packed_launch.md).
+// Block orbits (profiles/ablation_block_orbits.md): odd-pair orbits never close the even bonds (2,3), (4,5), .. in L2, and 56 % of
+// the tiles have too few flippable pairs to fill 2^6.  The packed launch builds its orbits from the leading SD_ORBIT_QUAD_BLOCKS
+// four-site blocks (all configurations of a block with the same filling: its three bonds close inside the orbit) up to a capacity
+// of SD_ORBIT_CAP_TENTHS / 10 bits, and deals every orbit to the queue with the fewest rows so far (SD_ORBIT_DEAL_ROWS), ties to
+// the lowest queue index.  Orbits now hold up to 192 tiles (216 with more blocks), and dealt round-robin they leave the eight queues 5-10 % apart in rows:
+// every block order was then SLOWER than odd pairs (L=32: 10.19-11.09 ms against 10.22), at 4, 5 and 6 workgroups per CU alike.
+// Dealt by rows (queues within 0.02 %) they win: L=32 10.51 -> 10.04 ms, L=30 2.45 -> 2.31; odd pairs dealt by rows gain 0.9 %.
+// (2 blocks, 7.8 bits) is the default; 6.2 bits loses 3 % to it, 7.2 bits 0.3 %, 3 blocks at 8.2 bits is 0.2 % faster at L=32 and
+// 1 % slower at L=30; five or six workgroups per CU (SD_PACK_WGS_PER_CU) gain nothing.  0 blocks, 60, no row dealing is the old table.
+#ifndef SD_ORBIT_QUAD_BLOCKS
+#define SD_ORBIT_QUAD_BLOCKS 2
+#endif
+#ifndef SD_ORBIT_CAP_TENTHS
+#define SD_ORBIT_CAP_TENTHS 78
+#endif
+#ifndef SD_ORBIT_DEAL_ROWS
+#define SD_ORBIT_DEAL_ROWS 1
+#endif
+static_assert(SD_ORBIT_QUAD_BLOCKS >= 0 && SD_ORBIT_CAP_TENTHS >= 0 && SD_ORBIT_CAP_TENTHS <= 150, "orbit member ids take 16 key bits");
+struct OrbitRule { int quad_blocks, cap_tenths; bool deal_rows; };
+static const OrbitRule XCD_RULE_CLASSES = {0, 50, false}, XCD_RULE_PACKED = {SD_ORBIT_QUAD_BLOCKS, SD_ORBIT_CAP_TENTHS, SD_ORBIT_DEAL_ROWS != 0};
 static std::vector<std::vector<size_t>> xcd_queues(const sd_model *m, int p, const std::vector<uint32_t> &tp_io,
-                                                   std::vector<int64_t> &first_seen, const int FO) {
+                                                   std::vector<int64_t> &first_seen, const OrbitRule rule) {
   std::vector<std::vector<size_t>> q(8);
   {
     const int CH = 32;
@@ -159,36 +181,39 @@ static std::vector<std::vector<size_t>> xcd_queues(const sd_model *m, int p, con
     // (Tried: with a wrap bond (1, j), j in the suffix -- the periodic chain's (L, 1) -- site 1 alone as an extra generator, so
     // that P and P ^ 1 are queued next to each other and the wrap bond's gather finds its partner tile in L2.  Periodic L=28 /
     // L=30: 0.775 / 3.127 ms with it, 0.770 / 3.117 without -- no gain, removed; profiles/ablation_r03.md section 5.)
-    // canonical orbit representative: chosen pairs set to (up, down); member id = what is flipped
+    // canonical orbit representative and member id: orbit_key.hpp
     auto canon = [&](uint32_t P, int *member_out) {
-      uint32_t C0 = P; int member = 0, ng = 0;
-      for (int b = 1; b + 1 <= p && ng < FO; b += 2)
-        if (((P >> (b - 1)) ^ (P >> b)) & 1u) {
-          if (!((P >> (b - 1)) & 1u)) { C0 ^= 3u << (b - 1); member |= 1 << ng; }
-          ++ng;
-        }
-      if (member_out) *member_out = member;
-      return C0;
+      const sd_orbit_key o = sd_orbit_key_of(P, p, rule.quad_blocks, rule.cap_tenths);
+      if (member_out) *member_out = (int)o.member;
+      return o.rep;
     };
     auto first_seen_reset = [&](uint32_t P) { first_seen[canon(P, nullptr)] = -1; };
     if (nt >= 64 && p >= 3 && count_nn_hops(m) > 0) {
-      std::vector<uint64_t> key(nt);     // (first-seen rank of the orbit) << 8 | member id
+      std::vector<uint64_t> key(nt);     // (first-seen rank of the orbit) << 16 | member id
       int64_t n_orb = 0;
       for (size_t k = 0; k < nt; ++k) {
         int member = 0;
         const uint32_t C0 = canon(tp_io[k], &member);
         if (first_seen[C0] < 0) first_seen[C0] = n_orb++;
-        key[k] = ((uint64_t)first_seen[C0] << 8) | (uint64_t)member;
+        key[k] = ((uint64_t)first_seen[C0] << 16) | (uint64_t)member;
       }
       std::vector<size_t> idx(nt);
       for (size_t k = 0; k < nt; ++k) idx[k] = k;
       std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
-      // deal whole orbits to the 8 XCD queues
+      // deal whole orbits to the 8 XCD queues: round-robin, or (deal_rows) to the queue with the fewest rows so far, ties to the
+      // lowest queue index
       size_t o = 0;
+      int64_t q_rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       for (size_t k = 0; k < nt;) {
         size_t e = k;
-        while (e < nt && (key[idx[e]] >> 8) == (key[idx[k]] >> 8)) ++e;
-        for (size_t t = k; t < e; ++t) q[o % 8].push_back(idx[t]);
+        while (e < nt && (key[idx[e]] >> 16) == (key[idx[k]] >> 16)) ++e;
+        size_t x = o % 8;
+        if (rule.deal_rows) {
+          x = 0;
+          for (size_t y = 1; y < 8; ++y) if (q_rows[y] < q_rows[x]) x = y;
+        }
+        for (size_t t = k; t < e; ++t) q[x].push_back(idx[t]);
+        q_rows[x] += (int64_t)(e - k) * B(m, m->LS, m->nup - __builtin_popcount(tp_io[idx[k]]));   // members have equal length
         ++o; k = e;
       }
       for (size_t k = 0; k < nt; ++k) first_seen_reset(tp_io[k]);
@@ -210,7 +235,7 @@ static std::vector<std::vector<size_t>> xcd_queues(const sd_model *m, int p, con
 
 static void xcd_order(const sd_model *m, int p, std::vector<uint32_t> &tp_io, std::vector<int64_t> &tb_io,
                       std::vector<int64_t> &first_seen) {
-  const std::vector<std::vector<size_t>> q = xcd_queues(m, p, tp_io, first_seen, XCD_FO_CLASSES);
+  const std::vector<std::vector<size_t>> q = xcd_queues(m, p, tp_io, first_seen, XCD_RULE_CLASSES);
   const size_t nt = tp_io.size();
   std::vector<uint32_t> tp; std::vector<int64_t> tb;
   tp.reserve(nt); tb.reserve(nt);
@@ -862,7 +887,7 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
       std::sort(by_base.begin(), by_base.end());
       std::vector<uint32_t> all((size_t)m->short_off);
       for (int k = 0; k < m->short_off; ++k) all[k] = by_base[k].second;
-      const std::vector<std::vector<size_t>> q = xcd_queues(m, p, all, xcd_scratch, XCD_FO_PACKED);
+      const std::vector<std::vector<size_t>> q = xcd_queues(m, p, all, xcd_scratch, XCD_RULE_PACKED);
       auto slots_of = [&](uint32_t P) { return (int)((B(m, m->LS, m->nup - __builtin_popcount(P)) + 255) / 256); };
       std::vector<std::vector<int32_t>> qb(8);                  // per queue: its blocks, four entries each
       for (int x = 0; x < 8; ++x) {
