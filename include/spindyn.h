@@ -454,6 +454,48 @@ int sd_dimer_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void 
                           double xy, double zz, double *D_out, double *e_out);
 int sd_dimer_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *bonds, int B,
                               double xy, double zz, double *D_out, double *e_out);
+/* ---- lattice symmetry operators: translation, reflection, spin flip ---------------------------------------------------------
+ * Site i is bit i - 1 of a configuration s; L-bit masks implied.
+ *   T moves the spin of site i to site i + 1 (mod L):  T s = ((s << 1) | (s >> (L - 1))) & mask;
+ *   R exchanges site i with site L + 1 - i: bit reversal over L bits;
+ *   Z flips every spin: ~s & mask -- defined on the full basis and on sectors with 2 nup = L only (SD_EARG elsewhere).
+ * A group element g = (r, refl, flip) is U_g = T^r R^refl Z^flip, U_g |s> = |T^r R^refl Z^flip s>, so
+ *   (U_g psi)[idx(s)] = psi[idx(Z^flip R^refl T^-r s)];   its CODE is r | refl << 8 | flip << 9 with 0 <= r < L.
+ * Nothing is divided by <psi|psi>.  Fixed-nup sectors and the full basis; unsharded models only.
+ *
+ * sd_model_symmetric: *yes = 1 when the hop, zz and field lists are invariant under U_g, else 0 (host only; works on a model created
+ *   without a context).  Bond tables are summed per unordered site pair, i == j and exact zeros dropped, and compared exactly after
+ *   the site permutation of T^r R^refl; the field must be invariant under that permutation, and all zero for flip = 1.
+ * sd_symmetry_apply: out (n elements of psi's dtype, every row written) = U_g psi -- a permutation, every output is bit for bit one
+ *   input -- or, with y != NULL, the fused out = U_g psi + (c_re + i c_im) y (y of psi's dtype, read row by row; a Float64 psi takes
+ *   c_im = 0).  _dev: device pointers; out_dev must not share a byte with psi_dev (SD_EARG: identity and partial overlap alike); it
+ *   may be y_dev itself, not a range that overlaps y_dev partly.
+ * sd_symmetry_overlaps: out[2k .. +1] (host) = (re, im) of <bra|U_g|ket> = sum_s conj(bra[s]) (U_g ket)[s] for element k of `codes`
+ *   (n_codes host ints, 1 .. SD_SYM_MAX_ELEMENTS), all in one pass over the rows; bra and ket of `dtype`, bra NULL: ket itself.  Sums
+ *   in a fixed order: the same call gives the same bits.
+ * sd_symmetry_project: out = sum_k c_k U_{g_k} psi, c_k = (coef[2k], coef[2k + 1]), in one pass; per row the terms are added in list
+ *   order from zero, each product formed first, no fused multiply-add.  dtype_out is SD_C128, or SD_F64 for an SD_F64 psi when every
+ *   coefficient is real (SD_EARG otherwise).  out_dev must not share a byte with psi_dev.
+ * _dev: the vectors are device pointers; sd_symmetry_apply_dev is queued on the context's stream, the other two synchronise it.
+ * SD_EARG: r outside 0..L-1 or other bits set in a code, Z in a sector with 2 nup != L, n_codes out of range, a NULL pointer, a dtype
+ * other than SD_F64 / SD_C128, coefficients that are not finite, out aliasing psi, a sharded model, a model without device tables.
+ * SD_EDIM: n is not the basis dimension.  A model with no rows gives empty vectors / zero overlaps. */
+#define SD_SYM_REFLECT 256
+#define SD_SYM_FLIP 512
+#define SD_SYM_MAX_ELEMENTS 252
+int sd_model_symmetric(const sd_model *m, int code, int *yes);
+int sd_symmetry_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int code, const void *y_host,
+                      double c_re, double c_im, void *out_host);
+int sd_symmetry_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int code, const void *y_dev,
+                          double c_re, double c_im, void *out_dev);
+int sd_symmetry_overlaps(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_host, const void *ket_host, int64_t n,
+                         const int *codes, int n_codes, double *out);
+int sd_symmetry_overlaps_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_dev, const void *ket_dev, int64_t n,
+                             const int *codes, int n_codes, double *out);
+int sd_symmetry_project(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *codes,
+                        const double *coef, int n_codes, int dtype_out, void *out_host);
+int sd_symmetry_project_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *codes,
+                            const double *coef, int n_codes, int dtype_out, void *out_dev);
 /* create_spin_operator(site, op)(psi, model)   src/Hamiltonian.jl:49-136.  site is 1-based.  S^z is diagonal and works
  * in any basis; S^+, S^-, S^x, S^y change the magnetisation and are rejected in a fixed-nup sector (SD_EARG), as the
  * reference does.  out has psi's element type; S^y needs a ComplexF64 psi (SD_EARG otherwise: the reference's

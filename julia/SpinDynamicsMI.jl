@@ -21,7 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
-       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, typicality_sample, typicality_correlation_function,
+       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -589,6 +589,83 @@ function dimer_correlations(psi::AbstractVector, model::Model; bonds=nothing, xy
                 (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cint}, Cint, Float64, Float64, Ptr{Float64}, Ptr{Float64}),
                 model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), flat, B, Float64(xy), Float64(zz), D, e), model.ctx.h)
     return permutedims(reshape(reinterpret(ComplexF64, D), B, B)), e     # the ABI is row-major
+end
+
+# ---- lattice symmetry operators (DESIGN.md 18): U_g = T^shift R^reflect Z^flip, code = shift | reflect << 8 | flip << 9 ----
+symmetry_code(model::Model; shift::Integer=0, reflect::Bool=false, flip::Bool=false) =
+    Cint(mod(shift, model.L) | (reflect ? 256 : 0) | (flip ? 512 : 0))
+
+# are the hop, zz and field lists invariant under U_g?  (host only)
+function is_symmetric(model::Model; kw...)
+    yes = Ref{Cint}(0)
+    check(ccall((:sd_model_symmetric, libspindyn), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}), model.h, symmetry_code(model; kw...), yes),
+          model.ctx.h)
+    return yes[] != 0
+end
+
+# U_g psi, or with y the fused U_g psi + c y; a vector of psi's element type
+function symmetry_apply(psi::AbstractVector, model::Model; y::Union{Nothing,AbstractVector}=nothing, c::Number=1.0, kw...)
+    p = hostvec(psi)
+    out = similar(p)
+    (y === nothing || length(y) == length(p)) || throw(DimensionMismatch("length(y) != length(psi)"))
+    yy = y === nothing ? Ptr{Cvoid}(C_NULL) : Vector{eltype(p)}(y)
+    check(ccall((:sd_symmetry_apply, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Float64, Float64, Ptr{Cvoid}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), symmetry_code(model; kw...), yy, Float64(real(c)),
+                Float64(imag(c)), out), model.ctx.h)
+    return out
+end
+translate(psi::AbstractVector, model::Model, r::Integer=1) = symmetry_apply(psi, model; shift=r)
+reflect(psi::AbstractVector, model::Model) = symmetry_apply(psi, model; reflect=true)
+spin_flip(psi::AbstractVector, model::Model) = symmetry_apply(psi, model; flip=true)
+
+# <bra|U_g|psi> for a vector of element codes (symmetry_code) from one pass; bra nothing: psi itself
+function symmetry_overlaps(psi::AbstractVector, model::Model, codes::AbstractVector{<:Integer}; bra::Union{Nothing,AbstractVector}=nothing)
+    (bra === nothing || length(bra) == length(psi)) || throw(DimensionMismatch("length(bra) != length(psi)"))
+    k = bra === nothing ? hostvec(psi) : Vector{ComplexF64}(psi)
+    b = bra === nothing ? Ptr{Cvoid}(C_NULL) : Vector{ComplexF64}(bra)
+    cl = Vector{Cint}(codes)
+    out = Vector{Float64}(undef, 2 * length(cl))
+    check(ccall((:sd_symmetry_overlaps, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cint}, Cint, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(k)), b, k, length(k), cl, length(cl), out), model.ctx.h)
+    return collect(reinterpret(ComplexF64, out))
+end
+
+# w_n = <psi|P_n|psi>, n = 0..L-1, P_n = (1/L) sum_r e^{+i k_n r} T^r
+function momentum_weights(psi::AbstractVector, model::Model)
+    L = model.L
+    ov = symmetry_overlaps(psi, model, [symmetry_code(model; shift=r) for r in 0:L-1])
+    return [real(sum(cis(2pi * n * r / L) * ov[r + 1] for r in 0:L-1)) / L for n in 0:L-1]
+end
+
+# sum_k coef[k] U_{codes[k]} psi in one pass (ComplexF64)
+function symmetry_combine(psi::AbstractVector, model::Model, codes::AbstractVector{<:Integer}, coef::AbstractVector{<:Number})
+    p = hostvec(psi)
+    cl = Vector{Cint}(codes)
+    cf = collect(reinterpret(Float64, Vector{ComplexF64}(coef)))
+    out = Vector{ComplexF64}(undef, length(p))
+    check(ccall((:sd_symmetry_project, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cint}, Ptr{Float64}, Cint, Cint, Ptr{Cvoid}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), cl, cf, length(cl), 2, out), model.ctx.h)
+    return out
+end
+
+# P psi: momentum n (P_n), parity +-1 ((1 +- R)/2), spin_flip +-1 ((1 +- Z)/2); parity with momentum only at n = 0 and n = L/2
+function symmetry_project(psi::AbstractVector, model::Model; momentum::Union{Nothing,Integer}=nothing,
+                          parity::Union{Nothing,Integer}=nothing, spin_flip::Union{Nothing,Integer}=nothing)
+    L = model.L
+    (momentum === nothing || 0 <= momentum < L) || throw(ArgumentError("momentum must be in 0..L-1"))
+    (parity === nothing || momentum === nothing || momentum == 0 || 2 * momentum == L) ||
+        throw(ArgumentError("parity combines with momentum only at n = 0 and n = L/2"))
+    codes = Cint[]; coef = ComplexF64[]
+    for r in (momentum === nothing ? (0:0) : (0:L-1)), refl in (parity === nothing ? (0:0) : (0:1)), fl in (spin_flip === nothing ? (0:0) : (0:1))
+        c = momentum === nothing ? complex(1.0) : cis(2pi * momentum * r / L) / L
+        c *= parity === nothing ? 1.0 : 0.5 * (refl == 1 ? parity : 1)
+        c *= spin_flip === nothing ? 1.0 : 0.5 * (fl == 1 ? spin_flip : 1)
+        push!(codes, Cint(r | (refl << 8) | (fl << 9))); push!(coef, c)
+    end
+    return symmetry_combine(psi, model, codes, coef)
 end
 
 # operator descriptors: (:Sz, site), (:Szq, q), :Sz_all (operator_i only), (:current, weights | nothing),

@@ -21,6 +21,8 @@ from .typicality import (chebyshev_imag_coeffs, current_expectation, dqt_sample,
 from .observables import (bond_energies, bond_operator, connected_correlations, correlation_matrix, dimer_correlation_matrix,
                           dimer_structure_factor, magnetization_per_site, model_bonds, momentum_distribution,
                           static_structure_factor, structure_factor_Sq)
+from .symmetry import (is_symmetric, lowest_level, momentum_weights, quantum_numbers, reflect, spin_flip, symmetric_operator,
+                       symmetry_apply, symmetry_combine, symmetry_overlaps, symmetry_project, translate)
 from . import initial_states
 from .initial_states import domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 from .api import dynamical_structure_factor, groundstate, structure_factor, time_evolve

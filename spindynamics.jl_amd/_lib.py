@@ -154,6 +154,13 @@ PROTOTYPES = {
     "sd_bond_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
     "sd_dimer_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _d, _d, _dp, _dp]),
     "sd_dimer_correlations_dev": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _d, _d, _dp, _dp]),
+    "sd_model_symmetric": (_i, [_vp, _i, _ip]),
+    "sd_symmetry_apply": (_i, [_vp, _vp, _i, _vp, _i64, _i, _vp, _d, _d, _vp]),
+    "sd_symmetry_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _vp, _d, _d, _vp]),
+    "sd_symmetry_overlaps": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _ip, _i, _dp]),
+    "sd_symmetry_overlaps_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _ip, _i, _dp]),
+    "sd_symmetry_project": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _dp, _i, _i, _vp]),
+    "sd_symmetry_project_dev": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _dp, _i, _i, _vp]),
     "sd_energy_current_terms": (_i, [_vp, _i, _vp, _i, _ip]),
     "sd_dcurrent_apply": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _i, _vp]),
     "sd_dcurrent_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _i, _vp]),

@@ -5,7 +5,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <new>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "sd_internal.hpp"
@@ -126,9 +129,61 @@ int check_apply_args(sd_ctx *ctx, const sd_model *m, int dtype, const void *out,
   SD_HIP(ctx, hipSetDevice(ctx->device));   // the caller's thread may have another device current (several contexts per process)
   return SD_OK;
 }
+// the site pairs of a bond list as a table: J summed per unordered pair in list order, i == j and exact zeros dropped, each pair
+// sent through the site permutation `perm` (1-based)
+std::map<std::pair<int, int>, double> bond_table(const std::vector<int> &bi, const std::vector<int> &bj, const std::vector<double> &J,
+                                                 const std::vector<int> &perm) {
+  std::map<std::pair<int, int>, double> sum, out;
+  for (size_t k = 0; k < J.size(); ++k) {
+    if (bi[k] == bj[k]) continue;
+    sum[{std::min(bi[k], bj[k]), std::max(bi[k], bj[k])}] += J[k];
+  }
+  for (const auto &e : sum) {
+    if (e.second == 0.0) continue;
+    const int a = perm[(size_t)e.first.first], b = perm[(size_t)e.first.second];
+    out[{std::min(a, b), std::max(a, b)}] = e.second;
+  }
+  return out;
+}
 }  // namespace
 
+int sd_symmetry_check_code(const sd_model *m, int code, std::string &err) {
+  const int r = code & 255;
+  if (code < 0 || (code >> 10) != 0 || r >= m->L) { err = "element code: the shift must be in 0..L-1 and no bit above bit 9 set"; return SD_EARG; }
+  if ((code & SD_SYM_FLIP) && m->nup >= 0 && 2 * m->nup != m->L) {
+    err = "the spin flip Z is defined on the full basis and on sectors with 2 nup = L only";
+    return SD_EARG;
+  }
+  return SD_OK;
+}
+
 extern "C" {
+
+int sd_model_symmetric(const sd_model *m, int code, int *yes) {
+  if (!m || !yes) return SD_EARG;
+  try {
+    std::string err;
+    const int rc = sd_symmetry_check_code(m, code, err);
+    if (rc) return m->ctx ? sd_set_err(m->ctx, rc, err) : rc;
+    const int L = m->L, r = code & 255;
+    std::vector<int> id((size_t)L + 1), perm((size_t)L + 1);       // site i -> the site T^r R^refl moves its spin to
+    for (int i = 1; i <= L; ++i) {
+      id[(size_t)i] = i;
+      const int j = (code & SD_SYM_REFLECT) ? L + 1 - i : i;
+      perm[(size_t)i] = (j - 1 + r) % L + 1;
+    }
+    bool ok = bond_table(m->hop_i, m->hop_j, m->hop_J, perm) == bond_table(m->hop_i, m->hop_j, m->hop_J, id) &&
+              bond_table(m->zz_i, m->zz_j, m->zz_J, perm) == bond_table(m->zz_i, m->zz_j, m->zz_J, id);
+    for (int i = 1; i <= L && ok; ++i) {
+      const double f = m->field[(size_t)i - 1];
+      ok = f == m->field[(size_t)perm[(size_t)i] - 1] && !((code & SD_SYM_FLIP) && f != 0.0);
+    }
+    *yes = ok ? 1 : 0;
+    return SD_OK;
+  } catch (...) {
+    return m->ctx ? sd_set_err(m->ctx, SD_ENOMEM, "out of host memory inside the call") : SD_ENOMEM;
+  }
+}
 
 const char *sd_version(void) { return "spindyn-mi355x 0.1 (gfx950)"; }
 

@@ -1970,6 +1970,114 @@ int dimer_correlations_core(sd_ctx *ctx, const sd_model *m, int dtype, const voi
   return SD_OK;
 }
 
+// ---- lattice symmetry operators (kernels_symmetry.hip) ----
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte?  (the gathers read rows of psi that other workgroups' rows of out
+// would overwrite: any overlap corrupts the result, not only out == psi)
+bool sym_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+int sym_code(sd_ctx *ctx, const sd_model *m, int code) {
+  std::string err;
+  const int rc = sd_symmetry_check_code(m, code, err);
+  return rc ? sd_set_err(ctx, rc, err) : SD_OK;
+}
+
+// a validated element list on the device: the coefficients (2 n doubles, when given) first, then the n codes
+struct SymList {
+  DBuf buf;
+  const int *codes = nullptr;
+  const double *coef = nullptr;
+  bool all_real = true;
+  int init(sd_ctx *ctx, const sd_model *m, const int *list, const double *c, int n) {
+    if (n < 1 || n > SD_SYM_MAX_ELEMENTS) return sd_set_err(ctx, SD_EARG, "the number of elements must be in 1..SD_SYM_MAX_ELEMENTS");
+    if (!list) return sd_set_err(ctx, SD_EARG, "null argument");
+    for (int k = 0; k < n; ++k) {
+      RC(sym_code(ctx, m, list[k]));
+      if (c && (!std::isfinite(c[2 * k]) || !std::isfinite(c[2 * k + 1]))) return sd_set_err(ctx, SD_EARG, "the coefficients must be finite");
+      if (c && c[2 * k + 1] != 0.0) all_real = false;
+    }
+    const int64_t nc = c ? 2 * (int64_t)n : 0;
+    RC(buf.alloc(ctx, nc + (n + 1) / 2));
+    if (c) RC(h2d(ctx, buf.p, c, nc));
+    RC(sd_xfer_h2d(ctx, buf.p + nc, list, sizeof(int) * (size_t)n));
+    coef = buf.p;
+    codes = (const int *)(buf.p + nc);
+    return SD_OK;
+  }
+};
+
+// out (n elements of psi's dtype) = U_g psi (+ c y)
+int symmetry_apply_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int code, const void *y, double cr,
+                        double ci, void *out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  RC(sym_code(ctx, m, code));
+  if (y && (!std::isfinite(cr) || !std::isfinite(ci))) return sd_set_err(ctx, SD_EARG, "the coefficient must be finite");
+  if (y && dtype == SD_F64 && ci != 0.0) return sd_set_err(ctx, SD_EARG, "a Float64 vector takes a real coefficient (c_im = 0)");
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!out || !psi) return sd_set_err(ctx, SD_EARG, "null argument");
+  const size_t vbytes = (size_t)n * (dtype == SD_C128 ? 16 : 8);
+  if (on_dev && sym_overlap(out, vbytes, psi, vbytes)) return sd_set_err(ctx, SD_EARG, "out must not alias or overlap psi");
+  if (on_dev && y && y != out && sym_overlap(out, vbytes, y, vbytes)) return sd_set_err(ctx, SD_EARG, "out may be y itself but must not overlap it partly");
+  DBuf in, yin, res;
+  const double *p = nullptr, *yp = nullptr;
+  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
+  if (y) RC(site_stage(ctx, dtype, y, on_dev, n, yin, &yp));
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  double *o = (double *)out;
+  if (!on_dev) { RC(res.alloc(ctx, nc * n)); o = res.p; }
+  RC(sd_launch_symmetry_apply(ctx, m, dtype, code, p, yp, cr, ci, o));
+  if (!on_dev) return d2h(ctx, out, o, nc * n);
+  return SD_OK;
+}
+
+// out (host, 2 n_codes doubles) = <bra|U_g|ket> for the elements of the list
+int symmetry_overlaps_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra, const void *ket, int64_t n, const int *codes,
+                           int n_codes, double *out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  if (!ket || !out) return sd_set_err(ctx, SD_EARG, "null argument");
+  SymList sl;
+  RC(sl.init(ctx, m, codes, nullptr, n_codes));
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  DBuf bin, kin, res;
+  const double *b = nullptr, *k = nullptr;
+  RC(site_stage(ctx, dtype, ket, on_dev, n, kin, &k));
+  b = k;
+  if (bra && bra != ket) RC(site_stage(ctx, dtype, bra, on_dev, n, bin, &b));
+  RC(res.alloc(ctx, 2 * (int64_t)n_codes));
+  RC(sd_launch_symmetry_overlaps(ctx, m, dtype, b, k, sl.codes, n_codes, res.p));
+  SD_HIP(ctx, hipMemcpyAsync(out, res.p, sizeof(double) * 2 * (size_t)n_codes, hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+
+// out (n elements of dtype_out) = sum_k c_k U_{g_k} psi
+int symmetry_project_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const int *codes, const double *coef,
+                          int n_codes, int dtype_out, void *out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  if (dtype_out != SD_F64 && dtype_out != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype_out must be SD_F64 or SD_C128");
+  if (!coef || !out || !psi) return sd_set_err(ctx, SD_EARG, "null argument");
+  SymList sl;
+  RC(sl.init(ctx, m, codes, coef, n_codes));
+  if (dtype_out == SD_F64 && dtype != SD_F64) return sd_set_err(ctx, SD_EARG, "an SD_F64 result needs an SD_F64 psi");
+  if (dtype_out == SD_F64 && !sl.all_real) return sd_set_err(ctx, SD_EARG, "an SD_F64 result needs real coefficients");
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (on_dev && sym_overlap(out, (size_t)n * (dtype_out == SD_C128 ? 16 : 8), psi, (size_t)n * (dtype == SD_C128 ? 16 : 8))) return sd_set_err(ctx, SD_EARG, "out must not alias or overlap psi");
+  DBuf in, res;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
+  const int nc = dtype_out == SD_C128 ? 2 : 1;
+  double *o = (double *)out;
+  if (!on_dev) { RC(res.alloc(ctx, nc * n)); o = res.p; }
+  RC(sd_launch_symmetry_project(ctx, m, dtype, p, sl.codes, sl.coef, n_codes, dtype_out, o));
+  if (!on_dev) return d2h(ctx, out, o, nc * n);
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));        // the list goes back to the pool
+  return SD_OK;
+}
+
 // an operator of the typicality driver: kind, site or momentum, device weights of a current, device tables of the energy current
 struct DqtOp {
   int kind = 0; int site = 0; double q = 0.0; DBuf wt; DList dl;
@@ -2107,6 +2215,31 @@ extern "C" int sd_dimer_correlations(sd_ctx *ctx, const sd_model *m, int dtype, 
 extern "C" int sd_dimer_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *bonds,
                                          int B, double xy, double zz, double *D_out, double *e_out) {
   return abi_guard(ctx, [&]() -> int { return dimer_correlations_core(ctx, m, dtype, psi_dev, n, bonds, B, xy, zz, D_out, e_out, true); });
+}
+
+extern "C" int sd_symmetry_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int code, const void *y_host,
+                                 double c_re, double c_im, void *out_host) {
+  return abi_guard(ctx, [&]() -> int { return symmetry_apply_core(ctx, m, dtype, psi_host, n, code, y_host, c_re, c_im, out_host, false); });
+}
+extern "C" int sd_symmetry_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int code,
+                                     const void *y_dev, double c_re, double c_im, void *out_dev) {
+  return abi_guard(ctx, [&]() -> int { return symmetry_apply_core(ctx, m, dtype, psi_dev, n, code, y_dev, c_re, c_im, out_dev, true); });
+}
+extern "C" int sd_symmetry_overlaps(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_host, const void *ket_host, int64_t n,
+                                    const int *codes, int n_codes, double *out) {
+  return abi_guard(ctx, [&]() -> int { return symmetry_overlaps_core(ctx, m, dtype, bra_host, ket_host, n, codes, n_codes, out, false); });
+}
+extern "C" int sd_symmetry_overlaps_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_dev, const void *ket_dev, int64_t n,
+                                        const int *codes, int n_codes, double *out) {
+  return abi_guard(ctx, [&]() -> int { return symmetry_overlaps_core(ctx, m, dtype, bra_dev, ket_dev, n, codes, n_codes, out, true); });
+}
+extern "C" int sd_symmetry_project(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *codes,
+                                   const double *coef, int n_codes, int dtype_out, void *out_host) {
+  return abi_guard(ctx, [&]() -> int { return symmetry_project_core(ctx, m, dtype, psi_host, n, codes, coef, n_codes, dtype_out, out_host, false); });
+}
+extern "C" int sd_symmetry_project_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *codes,
+                                       const double *coef, int n_codes, int dtype_out, void *out_dev) {
+  return abi_guard(ctx, [&]() -> int { return symmetry_project_core(ctx, m, dtype, psi_dev, n, codes, coef, n_codes, dtype_out, out_dev, true); });
 }
 
 extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, const void *r_host, uint64_t seed, int B_kind,

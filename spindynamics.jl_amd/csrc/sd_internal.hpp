@@ -333,6 +333,24 @@ int sd_dimer_tiles(int B);
 int sd_launch_dimer_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, const int *bonds_dev, int B, double xy, double zz,
                          double *dst);
 
+// Lattice symmetry operators (kernels_symmetry.hip): U_g = T^r R^refl Z^flip, code = r | refl << 8 | flip << 9, already
+// validated against the model by the caller (0 <= r < L, no other bits, Z only in the full basis or a half-filled sector).  Unsharded
+// models; queued on the context's stream, deterministic.
+// out (device, x's dtype, every row written; must not alias x) = U_g x, or U_g x + (cr + i ci) y when y != null (y may be out)
+int sd_launch_symmetry_apply(sd_ctx *ctx, const sd_model *m, int dtype, int code, const void *x, const void *y, double cr, double ci,
+                             void *out);
+// dst[2k .. +1] (device) = (re, im) of <bra|U_g|ket> for element k of codes_dev (ncodes <= SD_SYM_MAX_ELEMENTS device ints); bra and
+// ket of `dtype`
+int sd_launch_symmetry_overlaps(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra, const void *ket, const int *codes_dev,
+                                int ncodes, double *dst);
+// out (device, dtype_out) = sum_k c_k U_{g_k} psi, c_k = coef_dev[2k .. +1], summed in list order; dtype_out SD_F64 needs an SD_F64
+// psi (and real coefficients: the caller's check)
+int sd_launch_symmetry_project(sd_ctx *ctx, const sd_model *m, int dtype_in, const void *psi, const int *codes_dev,
+                               const double *coef_dev, int ncodes, int dtype_out, void *out);
+// an element code against a model (capi.cpp; host only): SD_EARG with a message in `err` for r outside 0..L-1, bits above bit 9, or Z
+// in a sector with 2 nup != L
+int sd_symmetry_check_code(const sd_model *m, int code, std::string &err);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.
