@@ -360,7 +360,9 @@ __device__ __forceinline__ void buf_load(double2 &v, __amdgpu_buffer_rsrc_t r, u
 }
 
 
-// counter-based N(0,1): element k of stream `seed` = Box-Muller on two uniforms hashed from (seed, k)
+// counter-based N(0,1): element k of stream `seed` = Box-Muller on two uniforms hashed from (seed, k).  sd_randn_at is the form
+// with the math libraries' log and cos, whose last bit differs between host and device; the library's streams are filled by
+// sd_randn (randn.hpp), the same formula in IEEE operations alone.
 __host__ __device__ inline uint64_t sd_mix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ULL;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;

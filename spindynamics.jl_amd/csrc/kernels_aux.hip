@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "device_common.hpp"
+#include "randn.hpp"
 
 using namespace sd_dev;
 
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(256) void k_fill_randn_tiles(sd_dev_model dm, doubl
     const int64_t lb = dm.tile_base[t], gb = dm.tile_gbase[t];
     const int len = (int)binom_g(dm, dm.LS, dm.nup - __popc(dm.tile_prefix[t]));
     for (int i = threadIdx.x; i < len * per; i += blockDim.x)
-      x[lb * per + i] = sd_randn_at(seed, (uint64_t)(gb * per + i));
+      x[lb * per + i] = sd_randn(seed, (uint64_t)(gb * per + i));
   }
 }
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.hpp"
+#include "randn.hpp"
 
 using sd_dev::block_reduce2;
 
@@ -642,7 +643,7 @@ __global__ __launch_bounds__(BS) void k_gemv_cols(double *__restrict__ y, const 
 
 __global__ __launch_bounds__(BS) void k_fill_randn(double *__restrict__ x, int64_t n, uint64_t seed, uint64_t first) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) x[i] = sd_dev::sd_randn_at(seed, first + (uint64_t)i);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) x[i] = sd_dev::sd_randn(seed, first + (uint64_t)i);
 }
 
 inline unsigned grid_for(int64_t n) {
@@ -654,7 +655,7 @@ inline unsigned grid_for(int64_t n) {
 
 }  // namespace
 
-double sd_randn_host(uint64_t seed, uint64_t k) { return sd_dev::sd_randn_at(seed, k); }
+double sd_randn_host(uint64_t seed, uint64_t k) { return sd_dev::sd_randn(seed, k); }
 
 int sd_k_dot(sd_ctx *ctx, int nc, const double *x, const double *y, int64_t N, int slot) {
   int rc = sd_ensure_partials(ctx, 2 * RED_BLOCKS); if (rc) return rc;

@@ -175,6 +175,32 @@ def test_randn_host_stream(pkg):
     assert abs(x.mean()) < 0.02 and abs(x.std() - 1) < 0.02
 
 
+def test_randn_host_stream_is_box_muller_of_the_hashed_uniforms(pkg):
+    """The stream's logarithm and cosine are written out in IEEE operations (csrc/randn.hpp) so that host and device agree to the
+    bit; here against numpy's: sqrt(-2 log u1) cos(2 pi u2) of the two uniforms hashed from (seed, index).  Bound: |x| <= sqrt(-2
+    log 2^-54) = 8.65; the restatement rounds its cosine's argument 2 pi u2 (absolute error up to 2 pi 2^-53 = 7e-16) and both
+    sides carry a few ulp (1.1e-16 each, 8 allowed) of relative error: 8.65 (7e-16 + 9e-16) < 1.5e-14."""
+    M = np.uint64
+
+    def mix(z):
+        z = z + M(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> M(30))) * M(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> M(27))) * M(0x94D049BB133111EB)
+        return z ^ (z >> M(31))
+    n = 400000
+    x = np.empty(n)
+    for seed, first in ((20260821, 0), (7, 987654321)):
+        assert pkg.lib().sd_fill_randn_host(x.ctypes.data_as(C.POINTER(C.c_double)), n, seed, first) == 0
+        with np.errstate(over="ignore"):                     # the hash wraps modulo 2^64
+            k = np.arange(n, dtype=M) + M(first)
+            h1, h2 = mix(M(seed) ^ mix(M(2) * k)), mix(M(seed) ^ mix(M(2) * k + M(1)))
+        u1 = ((h1 >> M(11)).astype(np.float64) + 0.5) / 9007199254740992.0
+        u2 = ((h2 >> M(11)).astype(np.float64) + 0.5) / 9007199254740992.0
+        want = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+        assert np.abs(x - want).max() <= 1.5e-14, (seed, first, np.abs(x - want).max())
+        assert np.abs(want).max() > 4.0
+
+
 def imported_rows(models, slabs, r):
     """Global basis index of every element of rank r's halo buffer, in halo order (both ownership modes)."""
     info = models[r].shard_info()
