@@ -496,6 +496,56 @@ int sd_symmetry_project(sd_ctx *ctx, const sd_model *m, int dtype, const void *p
                         const double *coef, int n_codes, int dtype_out, void *out_host);
 int sd_symmetry_project_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *codes,
                             const double *coef, int n_codes, int dtype_out, void *out_dev);
+/* ---- operator strings: any product of S^+, S^-, S^z, and sums of such products ------------------------------------------------
+ * Site i is bit i - 1 of a configuration s.  A TERM is (plus P, minus M, z Z, c, op): P, M, Z are 64-bit site masks, pairwise disjoint,
+ * with no bit at or above L; c = (c_re, c_im) is a complex coefficient; op >= 0 is the index of the operator the term belongs to:
+ *   O_k = sum_{t : op_t = k}  c_t  prod_{i in P_t} S^+_i  prod_{j in M_t} S^-_j  prod_{l in Z_t} S^z_l.
+ * All factors of a term sit on distinct sites, so their order does not matter.  In a fixed-nup sector every term must have
+ * |P| = |M| (SD_EARG otherwise); on the full basis any term is allowed (rows are configurations there).  A source sector different
+ * from the destination sector (as in sd_spm_q) is not covered.  Consecutive terms with equal (P, M, op) form a GROUP and share one
+ * gather.  Row form, as computed, nothing contracted:
+ *   (O psi)[s] = sum_groups [(s & P) == P and (s & M) == 0] co_g(s) psi[row(s ^ (P | M))]
+ *   co_g(s)    = sum over the group's terms, in list order from (0.0, 0.0), of sigma_t(s) ch_t,
+ *                sigma_t(s) = +1 when popcount(~s & Z_t) is even, else -1;  ch_t = c_t 2^-|Z_t| (scaled on the host, exact)
+ *   product:     t_re = co_re v_re - co_im v_im, t_im = co_re v_im + co_im v_re, both products first, then the add or subtract;
+ *                a Float64 psi: t_re = co_re v, t_im = co_im v
+ *   (re, im) accumulated from (0.0, 0.0) in group order.  A group with P = M = 0 is diagonal: its source is the row itself.
+ * Nothing is divided by <psi|psi>.  Fixed-nup sectors and the full basis; unsharded models only.
+ *
+ * sd_opstring_check: host only (works on a model created without a context).  Validates the list against the model, sets
+ *   *n_ops = K = 1 + the largest op (0 for an empty list) and *hermitian = 1 when, for every op, the list equals its own adjoint
+ *   (the adjoint of a term swaps P and M and conjugates c; coefficients of equal (P, M, Z) are summed first and compared exactly).
+ * sd_hamiltonian_terms: host only; the model's hop, zz and field lists as strings with op = 0, in list order: a hop (i, j, t) gives the
+ *   two terms t S^+_i S^-_j then t S^-_i S^+_j (none when i == j), a zz term (i, j, v) gives v with Z = {i, j} (v/4 with Z empty when
+ *   i == j), field entry i gives B_i with Z = {i}.  That order is part of the interface.  cap = 0: only *n_terms is set; SD_EARG for
+ *   0 < cap < *n_terms or more than SD_OPTERM_MAX terms.
+ * sd_opstring_apply: out (n elements of dtype_out, every row written) = O_0 psi, or with y != NULL the fused
+ *   out = O_0 psi + (b_re + i b_im) y: t = b y formed as the complex product above (a Float64 output: b_re y), then one add per
+ *   component; y has dtype_out.  Every term must have op = 0.  dtype_out is SD_C128, or SD_F64 for an SD_F64 psi when every c_im and
+ *   b_im is exactly 0.  _dev: device pointers, queued on the context's stream (a call with a non-empty list returns after the stream has
+ *   drained: its tables go back to the context's pool); out_dev must not share a byte with psi_dev (identity and partial overlap
+ *   alike); it may be y_dev itself, not a range that overlaps y_dev partly.
+ * sd_opstring_expect: out[2k .. +1] (host, 2 K doubles) = (re, im) of sum_s conj(bra[s]) (O_k ket)[s] for k = 0 .. K-1, all in one pass
+ *   over the rows, no vector O_k ket stored; bra and ket of `dtype`, bra NULL: ket itself.  Sums in a fixed order: the same call gives
+ *   the same bits.  Both forms synchronise the stream.
+ * SD_EARG: overlapping masks, a bit at or above L, |P| != |M| in a sector, a coefficient that is not finite, op < 0 or op >=
+ * SD_OPSTRING_MAX_OPS, n_terms outside 0..SD_OPTERM_MAX, op != 0 in the write form, an SD_F64 output with an imaginary coefficient or
+ * a ComplexF64 psi, another dtype, a NULL vector, out aliasing psi, a sharded model, a model without device tables.  SD_EDIM: n is not
+ * the basis dimension.  An empty list or a model with no rows gives a zero vector (b y with y) / zero expectations; the empty list has
+ * K = 0 and writes nothing to out of sd_opstring_expect. */
+#define SD_OPTERM_MAX 4096
+#define SD_OPSTRING_MAX_OPS 256
+typedef struct sd_opterm { uint64_t plus, minus, z; double c_re, c_im; int32_t op; int32_t reserved; } sd_opterm;
+int sd_opstring_check(const sd_model *m, const sd_opterm *terms, int n_terms, int *n_ops, int *hermitian);
+int sd_hamiltonian_terms(const sd_model *m, sd_opterm *out, int cap, int *n_terms);
+int sd_opstring_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_opterm *terms, int n_terms,
+                      const void *y_host, double b_re, double b_im, int dtype_out, void *out_host);
+int sd_opstring_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_opterm *terms,
+                          int n_terms, const void *y_dev, double b_re, double b_im, int dtype_out, void *out_dev);
+int sd_opstring_expect(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_host, const void *ket_host, int64_t n,
+                       const sd_opterm *terms, int n_terms, double *out);
+int sd_opstring_expect_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_dev, const void *ket_dev, int64_t n,
+                           const sd_opterm *terms, int n_terms, double *out);
 /* create_spin_operator(site, op)(psi, model)   src/Hamiltonian.jl:49-136.  site is 1-based.  S^z is diagonal and works
  * in any basis; S^+, S^-, S^x, S^y change the magnetisation and are rejected in a fixed-nup sector (SD_EARG), as the
  * reference does.  out has psi's element type; S^y needs a ComplexF64 psi (SD_EARG otherwise: the reference's

@@ -21,7 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
-       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, typicality_sample, typicality_correlation_function,
+       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -666,6 +666,111 @@ function symmetry_project(psi::AbstractVector, model::Model; momentum::Union{Not
         push!(codes, Cint(r | (refl << 8) | (fl << 9))); push!(coef, c)
     end
     return symmetry_combine(psi, model, codes, coef)
+end
+
+# ---- operator strings: any product of S^+, S^-, S^z, and sums of such products (DESIGN.md 19) ----
+# sd_opterm: c prod_{plus} S^+ prod_{minus} S^- prod_{z} S^z as a term of operator `op`; site i is bit i - 1 of the masks
+struct OpTerm
+    plus::UInt64
+    minus::UInt64
+    z::UInt64
+    c_re::Float64
+    c_im::Float64
+    op::Int32
+    reserved::Int32
+end
+
+sitebit(i::Integer) = UInt64(1) << (i - 1)
+
+# coeff * the product of the factors (:+, i), (:-, j), (:z, k), (:x, a), (:y, b) on distinct sites as a list of terms of operator
+# `op`; S^x = (S^+ + S^-)/2 and S^y = (S^+ - S^-)/(2i) are expanded here (the S^+ choice first)
+function op_string(coeff::Number, factors...; op::Integer=0)
+    plus = UInt64(0); minus = UInt64(0); z = UInt64(0); seen = UInt64(0)
+    xy = Tuple{Symbol,UInt64}[]
+    for (kind, site) in factors
+        b = sitebit(site)
+        (seen & b) == 0 || throw(ArgumentError("site $site appears twice in one string"))
+        seen |= b
+        if kind === :+
+            plus |= b
+        elseif kind === :-
+            minus |= b
+        elseif kind === :z
+            z |= b
+        elseif kind === :x || kind === :y
+            push!(xy, (kind, b))
+        else
+            throw(ArgumentError("unknown factor $kind: expected :+, :-, :z, :x or :y"))
+        end
+    end
+    out = OpTerm[]
+    for choice in 0:(1 << length(xy)) - 1
+        p = plus; m = minus; c = ComplexF64(coeff)
+        for (n, (kind, b)) in enumerate(xy)
+            lower = (choice >> (length(xy) - n)) & 1 == 1
+            if lower
+                m |= b
+                c = kind === :x ? 0.5 * c : complex(-0.5 * imag(c), 0.5 * real(c))
+            else
+                p |= b
+                c = kind === :x ? 0.5 * c : complex(0.5 * imag(c), -0.5 * real(c))
+            end
+        end
+        push!(out, OpTerm(p, m, z, real(c), imag(c), Int32(op), Int32(0)))
+    end
+    return out
+end
+
+operator_adjoint(terms::Vector{OpTerm}) = OpTerm[OpTerm(t.minus, t.plus, t.z, t.c_re, -t.c_im, t.op, Int32(0)) for t in terms]
+
+# (K, hermitian) of a list against a model: K = 1 + the largest op
+function operator_check(model::Model, terms::Vector{OpTerm})
+    k = Ref{Cint}(0); h = Ref{Cint}(0)
+    check(ccall((:sd_opstring_check, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cint}),
+                model.h, terms, length(terms), k, h), model.ctx.h)
+    return Int(k[]), h[] != 0
+end
+
+# the model's hop, zz and field lists as strings of op 0, in list order
+function hamiltonian_terms(model::Model)
+    n = Ref{Cint}(0)
+    check(ccall((:sd_hamiltonian_terms, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cint}), model.h, C_NULL, 0, n), model.ctx.h)
+    out = Vector{OpTerm}(undef, n[])
+    n[] == 0 && return out
+    check(ccall((:sd_hamiltonian_terms, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cint}), model.h, out, length(out), n), model.ctx.h)
+    return out
+end
+
+# O psi for a list whose terms all have op = 0 (ComplexF64), or O psi + b y with y
+function operator_apply(psi::AbstractVector, model::Model, terms::Vector{OpTerm}; y::Union{Nothing,AbstractVector}=nothing, b::Number=1.0)
+    x = hostvec(psi)
+    (y === nothing || length(y) == length(x)) || throw(DimensionMismatch("length(y) != length(psi)"))
+    yv = y === nothing ? Ptr{Cvoid}(C_NULL) : Vector{ComplexF64}(y)
+    out = Vector{ComplexF64}(undef, length(x))
+    check(ccall((:sd_opstring_apply, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Float64, Float64, Cint, Ptr{Cvoid}),
+                model.ctx.h, model.h, dtype_code(eltype(x)), x, length(x), terms, length(terms), yv, Float64(real(b)), Float64(imag(b)), 2, out),
+          model.ctx.h)
+    return out
+end
+
+# <bra|O_k|ket> for the K operators of the list from one pass; bra nothing: ket itself
+function operator_expectations(ket::AbstractVector, model::Model, terms::Vector{OpTerm}; bra::Union{Nothing,AbstractVector}=nothing)
+    (bra === nothing || length(bra) == length(ket)) || throw(DimensionMismatch("length(bra) != length(ket)"))
+    k = bra === nothing ? hostvec(ket) : Vector{ComplexF64}(ket)
+    b = bra === nothing ? Ptr{Cvoid}(C_NULL) : Vector{ComplexF64}(bra)
+    K = isempty(terms) ? 0 : Int(maximum(t.op for t in terms)) + 1
+    out = zeros(Float64, 2 * max(K, 1))
+    check(ccall((:sd_opstring_expect, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(k)), b, k, length(k), terms, length(terms), out), model.ctx.h)
+    return collect(reinterpret(ComplexF64, out))[1:K]
+end
+
+# -<S^z_i exp(i pi sum_{i<l<j} S^z_l) S^z_j>: one diagonal term, exp(i pi S^z) = 2i S^z
+function string_order(psi::AbstractVector, model::Model, i::Integer, j::Integer)
+    1 <= i < j || throw(ArgumentError("string_order needs sites 1 <= i < j"))
+    return operator_expectations(psi, model, op_string(-(2im)^(j - i - 1), [(:z, l) for l in i:j]...))[1]
 end
 
 # operator descriptors: (:Sz, site), (:Szq, q), :Sz_all (operator_i only), (:current, weights | nothing),

@@ -23,6 +23,10 @@ from .observables import (bond_energies, bond_operator, connected_correlations, 
                           static_structure_factor, structure_factor_Sq)
 from .symmetry import (is_symmetric, lowest_level, momentum_weights, quantum_numbers, reflect, spin_flip, symmetric_operator,
                        symmetry_apply, symmetry_combine, symmetry_overlaps, symmetry_project, translate)
+from .operators import (Term, chirality_correlations, chirality_terms, hamiltonian_terms, multi_spin_expectation,
+                        op_string, operator_adjoint, operator_apply, operator_check, operator_expectations,
+                        operator_groundstate, operator_hamiltonian, operator_is_hermitian, operator_simplify, pack_terms,
+                        scalar_chirality, string_order, string_order_terms)
 from . import initial_states
 from .initial_states import domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 from .api import dynamical_structure_factor, groundstate, structure_factor, time_evolve

@@ -161,6 +161,12 @@ PROTOTYPES = {
     "sd_symmetry_overlaps_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _ip, _i, _dp]),
     "sd_symmetry_project": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _dp, _i, _i, _vp]),
     "sd_symmetry_project_dev": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _dp, _i, _i, _vp]),
+    "sd_opstring_check": (_i, [_vp, _vp, _i, _ip, _ip]),
+    "sd_hamiltonian_terms": (_i, [_vp, _vp, _i, _ip]),
+    "sd_opstring_apply": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _i, _vp, _d, _d, _i, _vp]),
+    "sd_opstring_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _i, _vp, _d, _d, _i, _vp]),
+    "sd_opstring_expect": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, _i, _dp]),
+    "sd_opstring_expect_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, _i, _dp]),
     "sd_energy_current_terms": (_i, [_vp, _i, _vp, _i, _ip]),
     "sd_dcurrent_apply": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _i, _vp]),
     "sd_dcurrent_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _i, _vp]),

@@ -157,6 +157,62 @@ int sd_symmetry_check_code(const sd_model *m, int code, std::string &err) {
   return SD_OK;
 }
 
+// ---- operator strings: a caller's list against a model, cut into the device tables ----
+int sd_opstring_build(const sd_model *m, const sd_opterm *list, int n_terms, sd_opstring_tables &out, std::string &err) {
+  if (n_terms < 0 || n_terms > SD_OPTERM_MAX) { err = "the number of terms must be in 0..SD_OPTERM_MAX"; return SD_EARG; }
+  if (n_terms > 0 && !list) { err = "null argument"; return SD_EARG; }
+  if (m->L < 1 || m->L > SD_MAX_L) { err = "operator strings need 1 <= L <= 63"; return SD_EARG; }
+  const uint64_t outside = ~(~(uint64_t)0 >> (64 - m->L));
+  out = sd_opstring_tables();
+  out.terms.resize((size_t)n_terms);
+  std::vector<sd_opgroup> g;
+  int max_op = -1;
+  for (int n = 0; n < n_terms; ++n) {
+    const sd_opterm &T = list[n];
+    if ((T.plus & T.minus) || (T.plus & T.z) || (T.minus & T.z)) { err = "the plus, minus and z masks of a term must be pairwise disjoint"; return SD_EARG; }
+    if ((T.plus | T.minus | T.z) & outside) { err = "a mask of a term has a bit at or above L"; return SD_EARG; }
+    if (m->nup >= 0 && __builtin_popcountll(T.plus) != __builtin_popcountll(T.minus)) {
+      err = "in a fixed-nup sector every term needs as many S^+ as S^- factors";
+      return SD_EARG;
+    }
+    if (!std::isfinite(T.c_re) || !std::isfinite(T.c_im)) { err = "the coefficients must be finite"; return SD_EARG; }
+    if (T.op < 0 || T.op >= SD_OPSTRING_MAX_OPS) { err = "op must be in 0..SD_OPSTRING_MAX_OPS-1"; return SD_EARG; }
+    if (T.c_im != 0.0) out.all_real = false;
+    max_op = std::max(max_op, (int)T.op);
+    if (n == 0 || T.plus != list[n - 1].plus || T.minus != list[n - 1].minus || T.op != list[n - 1].op)
+      g.push_back(sd_opgroup{T.plus, T.minus, n, 0, T.op, 0});
+    ++g.back().count;
+    const double sc = std::ldexp(1.0, -__builtin_popcountll(T.z));      // 2^-|Z|: exact
+    out.terms[(size_t)n] = sd_opterm_dev{T.z, T.c_re * sc, T.c_im * sc};
+  }
+  out.n_ops = max_op + 1;
+  std::stable_sort(g.begin(), g.end(), [](const sd_opgroup &a, const sd_opgroup &b) { return a.op < b.op; });
+  out.op_first.assign((size_t)out.n_ops + 1, 0);
+  for (const sd_opgroup &G : g) ++out.op_first[(size_t)G.op + 1];
+  for (int k = 0; k < out.n_ops; ++k) out.op_first[(size_t)k + 1] += out.op_first[(size_t)k];
+  out.groups = std::move(g);
+  return SD_OK;
+}
+
+bool sd_opstring_hermitian(const sd_opterm *list, int n_terms) {
+  struct Key {
+    int32_t op; uint64_t p, m, z;
+    bool operator<(const Key &o) const { return op != o.op ? op < o.op : p != o.p ? p < o.p : m != o.m ? m < o.m : z < o.z; }
+  };
+  std::map<Key, std::pair<double, double>> sum;
+  for (int n = 0; n < n_terms; ++n) {
+    auto &s = sum[Key{list[n].op, list[n].plus, list[n].minus, list[n].z}];
+    s.first += list[n].c_re; s.second += list[n].c_im;
+  }
+  for (const auto &e : sum) {
+    const double re = e.second.first, im = e.second.second;
+    const auto it = sum.find(Key{e.first.op, e.first.m, e.first.p, e.first.z});      // the adjoint term: P <-> M, conj(c)
+    const double are = it == sum.end() ? 0.0 : it->second.first, aim = it == sum.end() ? 0.0 : it->second.second;
+    if (re != are || im != -aim) return false;
+  }
+  return true;
+}
+
 extern "C" {
 
 int sd_model_symmetric(const sd_model *m, int code, int *yes) {

@@ -147,6 +147,22 @@ __device__ __forceinline__ int64_t bond_partner(const sd_dev_model &dm, const in
   return ((s >> bj) & 1) ? idx - d : idx + d;
 }
 
+// Row of an arbitrary configuration t of the basis (kernels_opstring.hip).  MODE as above: 2 the configuration itself; 1 the plan's
+// own rank addr[prefix of t] + suf_rank[suffix of t], two cached loads; 0 the combinadic rank walked over the caller's LDS copy of
+// the binomials, lbin[n * K + k] = C(n, k), n < L, k < K = nup + 1.  t must have nup bits set below bit L (MODES 0 and 1).
+template <int MODE>
+__device__ __forceinline__ int64_t config_row(const sd_dev_model &dm, const int64_t *lbin, int K, uint64_t t) {
+  if (MODE == 2) return (int64_t)t;
+  if (MODE == 1) return dm.addr[(uint32_t)t & (((uint32_t)1 << dm.p) - 1u)] + (int64_t)dm.suf_rank[t >> dm.p];
+  int64_t idx = 0;
+  int r = dm.nup;
+  for (int b = 0; b < dm.L && r > 0; ++b) {
+    if ((t >> b) & 1) --r;
+    else idx += lbin[(dm.L - 1 - b) * K + r - 1];
+  }
+  return idx;
+}
+
 // ---- epilogue: what is stored for row `row` given acc = (H psi)[row] ----
 struct EpiSums { double s0, s1; };
 

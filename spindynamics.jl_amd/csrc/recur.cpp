@@ -2078,6 +2078,90 @@ int symmetry_project_core(sd_ctx *ctx, const sd_model *m, int dtype, const void 
   return SD_OK;
 }
 
+// ---- operator strings (kernels_opstring.hip) ----
+// A caller's list validated, cut into groups and put on the device: the three tables in one block from the context's pool (groups, 4
+// doubles each; terms, 3 doubles each; op_first).  n_groups == 0: the empty list.
+struct OpList {
+  DBuf buf;
+  sd_opstring_tables tab;
+  int n_groups = 0;
+  const sd_opgroup *groups = nullptr;
+  const sd_opterm_dev *terms = nullptr;
+  const int32_t *op_first = nullptr;
+  int init(sd_ctx *ctx, const sd_model *m, const sd_opterm *list, int n_terms) {
+    std::string err;
+    const int rc = sd_opstring_build(m, list, n_terms, tab, err);
+    if (rc) return sd_set_err(ctx, rc, err);
+    n_groups = (int)tab.groups.size();
+    if (n_groups == 0) return SD_OK;
+    static_assert(sizeof(sd_opgroup) == 32 && sizeof(sd_opterm_dev) == 24, "table layout");
+    const int64_t ng = 4 * (int64_t)tab.groups.size(), nt = 3 * (int64_t)tab.terms.size();
+    RC(buf.alloc(ctx, ng + nt + ((int64_t)tab.op_first.size() + 1) / 2));
+    groups = (const sd_opgroup *)buf.p;
+    terms = (const sd_opterm_dev *)(buf.p + ng);
+    op_first = (const int32_t *)(buf.p + ng + nt);
+    RC(sd_xfer_h2d(ctx, buf.p, tab.groups.data(), sizeof(sd_opgroup) * tab.groups.size()));
+    RC(sd_xfer_h2d(ctx, buf.p + ng, tab.terms.data(), sizeof(sd_opterm_dev) * tab.terms.size()));
+    return sd_xfer_h2d(ctx, buf.p + ng + nt, tab.op_first.data(), sizeof(int32_t) * tab.op_first.size());
+  }
+};
+
+// out (n elements of dtype_out) = O_0 psi (+ (b_re + i b_im) y, y of dtype_out)
+int opstring_apply_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const sd_opterm *list, int n_terms,
+                        const void *y, double b_re, double b_im, int dtype_out, void *out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  if (dtype_out != SD_F64 && dtype_out != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype_out must be SD_F64 or SD_C128");
+  OpList ol;
+  RC(ol.init(ctx, m, list, n_terms));
+  for (int k = 0; k < n_terms; ++k)
+    if (list[k].op != 0) return sd_set_err(ctx, SD_EARG, "the write form takes one operator: every term must have op = 0");
+  if (y && (!std::isfinite(b_re) || !std::isfinite(b_im))) return sd_set_err(ctx, SD_EARG, "the coefficient b must be finite");
+  if (dtype_out == SD_F64 && dtype != SD_F64) return sd_set_err(ctx, SD_EARG, "an SD_F64 output needs an SD_F64 psi");
+  if (dtype_out == SD_F64 && !ol.tab.all_real) return sd_set_err(ctx, SD_EARG, "an SD_F64 output needs real coefficients (every c_im = 0)");
+  if (dtype_out == SD_F64 && y && b_im != 0.0) return sd_set_err(ctx, SD_EARG, "an SD_F64 output takes a real b (b_im = 0)");
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!out || !psi) return sd_set_err(ctx, SD_EARG, "null argument");
+  const int nco = dtype_out == SD_C128 ? 2 : 1;
+  const size_t obytes = (size_t)n * 8 * (size_t)nco, pbytes = (size_t)n * (dtype == SD_C128 ? 16 : 8);
+  if (on_dev && sym_overlap(out, obytes, psi, pbytes)) return sd_set_err(ctx, SD_EARG, "out must not alias or overlap psi");
+  if (on_dev && y && y != out && sym_overlap(out, obytes, y, obytes)) return sd_set_err(ctx, SD_EARG, "out may be y itself but must not overlap it partly");
+  DBuf in, yin, res;
+  const double *p = nullptr, *yp = nullptr;
+  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
+  if (y) RC(site_stage(ctx, dtype_out, y, on_dev, n, yin, &yp));
+  double *o = (double *)out;
+  if (!on_dev) { RC(res.alloc(ctx, nco * n)); o = res.p; }
+  RC(sd_launch_opstring(ctx, m, dtype, p, ol.groups, ol.n_groups, ol.terms, yp, b_re, b_im, dtype_out, o));
+  if (!on_dev) return d2h(ctx, out, o, nco * n);
+  if (ol.n_groups > 0) SD_HIP(ctx, hipStreamSynchronize(ctx->stream));        // the tables go back to the pool
+  return SD_OK;
+}
+
+// out (host, 2 K doubles, K = 1 + max op) = <bra|O_k|ket>
+int opstring_expect_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra, const void *ket, int64_t n, const sd_opterm *list,
+                         int n_terms, double *out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  OpList ol;
+  RC(ol.init(ctx, m, list, n_terms));
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!ket) return sd_set_err(ctx, SD_EARG, "null argument");
+  const int K = ol.tab.n_ops;
+  if (K == 0) return SD_OK;                                  // the empty list: no operator, nothing to write
+  if (!out) return sd_set_err(ctx, SD_EARG, "null argument");
+  DBuf bin, kin, res;
+  const double *b = nullptr, *k = nullptr;
+  RC(site_stage(ctx, dtype, ket, on_dev, n, kin, &k));
+  b = k;
+  if (bra && bra != ket) RC(site_stage(ctx, dtype, bra, on_dev, n, bin, &b));
+  RC(res.alloc(ctx, 2 * (int64_t)K));
+  RC(sd_launch_opstring_expect(ctx, m, dtype, b, k, ol.groups, ol.op_first, ol.terms, K, res.p));
+  SD_HIP(ctx, hipMemcpyAsync(out, res.p, sizeof(double) * 2 * (size_t)K, hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+
 // an operator of the typicality driver: kind, site or momentum, device weights of a current, device tables of the energy current
 struct DqtOp {
   int kind = 0; int site = 0; double q = 0.0; DBuf wt; DList dl;
@@ -2240,6 +2324,62 @@ extern "C" int sd_symmetry_project(sd_ctx *ctx, const sd_model *m, int dtype, co
 extern "C" int sd_symmetry_project_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *codes,
                                        const double *coef, int n_codes, int dtype_out, void *out_dev) {
   return abi_guard(ctx, [&]() -> int { return symmetry_project_core(ctx, m, dtype, psi_dev, n, codes, coef, n_codes, dtype_out, out_dev, true); });
+}
+
+extern "C" int sd_opstring_check(const sd_model *m, const sd_opterm *terms, int n_terms, int *n_ops, int *hermitian) {
+  return abi_guard(nullptr, [&]() -> int {
+    if (!m || !n_ops || !hermitian) return SD_EARG;
+    sd_opstring_tables tab;
+    std::string err;
+    const int rc = sd_opstring_build(m, terms, n_terms, tab, err);
+    if (rc) return m->ctx ? sd_set_err(m->ctx, rc, err) : rc;
+    *n_ops = tab.n_ops;
+    *hermitian = sd_opstring_hermitian(terms, n_terms) ? 1 : 0;
+    return SD_OK;
+  });
+}
+extern "C" int sd_hamiltonian_terms(const sd_model *m, sd_opterm *out, int cap, int *n_terms) {
+  return abi_guard(nullptr, [&]() -> int {
+    if (!m || !n_terms || cap < 0 || (cap > 0 && !out)) return SD_EARG;
+    auto fail = [&](const char *msg) { return m->ctx ? sd_set_err(m->ctx, SD_EARG, msg) : SD_EARG; };
+    if (m->L < 1 || m->L > SD_MAX_L) return fail("operator strings need 1 <= L <= 63");
+    auto bit = [](int site) { return (uint64_t)1 << (site - 1); };
+    std::vector<sd_opterm> list;
+    for (size_t b = 0; b < m->hop_J.size(); ++b) {           // t (S^+_i S^-_j + S^-_i S^+_j); i == j never flips
+      const int i = m->hop_i[b], j = m->hop_j[b];
+      if (i == j) continue;
+      list.push_back(sd_opterm{bit(i), bit(j), 0, m->hop_J[b], 0.0, 0, 0});
+      list.push_back(sd_opterm{bit(j), bit(i), 0, m->hop_J[b], 0.0, 0, 0});
+    }
+    for (size_t b = 0; b < m->zz_J.size(); ++b) {            // v S^z_i S^z_j; i == j: (S^z_i)^2 = 1/4
+      const int i = m->zz_i[b], j = m->zz_j[b];
+      if (i == j) list.push_back(sd_opterm{0, 0, 0, 0.25 * m->zz_J[b], 0.0, 0, 0});
+      else list.push_back(sd_opterm{0, 0, bit(i) | bit(j), m->zz_J[b], 0.0, 0, 0});
+    }
+    for (int i = 1; i <= m->L && i <= (int)m->field.size(); ++i) list.push_back(sd_opterm{0, 0, bit(i), m->field[(size_t)i - 1], 0.0, 0, 0});
+    if (list.size() > SD_OPTERM_MAX) return fail("the model's lists give more than SD_OPTERM_MAX terms");
+    *n_terms = (int)list.size();
+    if (cap == 0) return SD_OK;
+    if ((size_t)cap < list.size()) return fail("cap is smaller than the number of terms");
+    std::copy(list.begin(), list.end(), out);
+    return SD_OK;
+  });
+}
+extern "C" int sd_opstring_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_opterm *terms,
+                                 int n_terms, const void *y_host, double b_re, double b_im, int dtype_out, void *out_host) {
+  return abi_guard(ctx, [&]() -> int { return opstring_apply_core(ctx, m, dtype, psi_host, n, terms, n_terms, y_host, b_re, b_im, dtype_out, out_host, false); });
+}
+extern "C" int sd_opstring_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_opterm *terms,
+                                     int n_terms, const void *y_dev, double b_re, double b_im, int dtype_out, void *out_dev) {
+  return abi_guard(ctx, [&]() -> int { return opstring_apply_core(ctx, m, dtype, psi_dev, n, terms, n_terms, y_dev, b_re, b_im, dtype_out, out_dev, true); });
+}
+extern "C" int sd_opstring_expect(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_host, const void *ket_host, int64_t n,
+                                  const sd_opterm *terms, int n_terms, double *out) {
+  return abi_guard(ctx, [&]() -> int { return opstring_expect_core(ctx, m, dtype, bra_host, ket_host, n, terms, n_terms, out, false); });
+}
+extern "C" int sd_opstring_expect_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_dev, const void *ket_dev, int64_t n,
+                                      const sd_opterm *terms, int n_terms, double *out) {
+  return abi_guard(ctx, [&]() -> int { return opstring_expect_core(ctx, m, dtype, bra_dev, ket_dev, n, terms, n_terms, out, true); });
 }
 
 extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, const void *r_host, uint64_t seed, int B_kind,

@@ -351,6 +351,40 @@ int sd_launch_symmetry_project(sd_ctx *ctx, const sd_model *m, int dtype_in, con
 // in a sector with 2 nup != L
 int sd_symmetry_check_code(const sd_model *m, int code, std::string &err);
 
+// Operator strings (kernels_opstring.hip): O_k = sum_t c_t prod_{P_t} S^+ prod_{M_t} S^- prod_{Z_t} S^z.  Device tables
+// of a validated list (sd_opstring_tables): one sd_opgroup per run of consecutive terms with equal (plus, minus, op), the groups of
+// operator k in list order at groups[op_first[k] .. op_first[k + 1]), one sd_opterm_dev per term (in list order).
+struct sd_opgroup {
+  uint64_t plus, minus;   // site masks: the row s contributes when (s & plus) == plus and (s & minus) == 0; source s ^ (plus | minus)
+  int32_t first, count;   // the group's terms: terms[first .. first + count)
+  int32_t op, pad;
+};
+struct sd_opterm_dev {
+  uint64_t z;             // sites of the S^z factors
+  double ch_re, ch_im;    // c * 2^-|z| (exact)
+};
+struct sd_opstring_tables {
+  std::vector<sd_opgroup> groups;
+  std::vector<sd_opterm_dev> terms;
+  std::vector<int32_t> op_first;   // n_ops + 1 entries
+  int n_ops = 0;
+  bool all_real = true;            // every c_im is exactly 0
+};
+// Validates a caller's list against the model and cuts it into the tables (capi.cpp; host only).  SD_EARG with a message in `err`:
+// see sd_opstring_check in include/spindyn.h.
+int sd_opstring_build(const sd_model *m, const sd_opterm *list, int n_terms, sd_opstring_tables &out, std::string &err);
+// is every operator of the list equal to its own adjoint? (coefficients of equal (plus, minus, z) summed first, compared exactly)
+bool sd_opstring_hermitian(const sd_opterm *list, int n_terms);
+// out (device, NCO components per row, every row written; must not alias psi) = O_0 psi, or O_0 psi + (b_re + i b_im) y when y != null
+// (y of the output dtype; may be out).  dtype_out SD_F64 needs an SD_F64 psi, real coefficients and b_im == 0 (the caller's check).
+// n_groups == 0: O = 0.  Unsharded models; queued on the context's stream.
+int sd_launch_opstring(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, const sd_opgroup *groups_dev, int n_groups,
+                       const sd_opterm_dev *terms_dev, const void *y, double b_re, double b_im, int dtype_out, void *out);
+// dst[2k .. +1] (device) = (re, im) of sum_s conj(bra[s]) (O_k ket)[s], k < n_ops (1 .. SD_OPSTRING_MAX_OPS), in one pass; bra and ket of
+// `dtype`.  op_first_dev: n_ops + 1 device ints.  Deterministic: the grid depends on the plan and n_ops alone.
+int sd_launch_opstring_expect(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra, const void *ket, const sd_opgroup *groups_dev,
+                              const int32_t *op_first_dev, const sd_opterm_dev *terms_dev, int n_ops, double *dst);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.
