@@ -1,5 +1,5 @@
 """Plain restatements, row by row, of the operators whose kernels walk the basis: the combinadic order of a sector's rows, the
-spin current, S^z_q, the site S^z signs and the single-site spin operators.  They share nothing with the library or the oracle.
+spin current, S^z_q, S^-_q / S^+_q between adjacent sectors, the site S^z signs and the single-site spin operators.  They share nothing with the library or the oracle.
 
 Sites are 1-based, site i <-> bit i - 1; a sector's rows are ordered lexicographically over the sorted lists of up sites (site 1
 first), the full basis by the configuration integer.  `unrank` / `rank` are numpy; the `*_t` functions are their torch ports and
@@ -8,7 +8,7 @@ lives.  Configurations are int64 there (L <= 62).
 
 Every floating-point result is built from single multiplies and adds of float64 tensors -- one torch call per operation, so
 nothing is contracted into a fused multiply-add -- in the order the row loop states; tests/test_rows_ref_host.py proves the
-current against tests/typicality_ref.py bit for bit."""
+current against tests/typicality_ref.py and S^-+_q against tests/transverse_ref.py, bit for bit."""
 import math
 from math import comb
 
@@ -167,6 +167,41 @@ def szq_rows(psi, s, L, q):
         xr, xi = psi.real, psi.imag
         return torch.complex(ar * xr - ai * xi, ar * xi + ai * xr)
     return torch.complex(ar * psi, ai * psi)
+
+
+# ---- S^-_q / S^+_q between adjacent sectors ------------------------------------------------------------------------------
+def spm_rows_t(psi, s_dst, L, nup_src, q, op):
+    """(S^-_q psi) (op "minus") or (S^+_q psi) (op "plus") at the TARGET configurations s_dst (int64 tensor) -> (re, im), float64
+    tensors on s_dst's device.  psi: the whole source vector (float64 or complex128) of sector nup_src, or of the full basis
+    when nup_src is None (row = configuration).
+
+    The row loop: zero accumulators; r = 0 .. L-1 ascending; a row whose bit r is 0 (minus) / 1 (plus) receives psi x at the
+    row of the configuration with that bit flipped -- `rank_t` of it in the source sector -- as re += c_r x.re - s_r x.im,
+    im += c_r x.im + s_r x.re (a real psi enters with x.im = 0), every product and sum a torch call of its own; then
+    (nf re, nf im).  c_r, s_r = math.cos(q r), math.sin(q r) and nf = 1 / math.sqrt(L) are Python floats."""
+    import torch
+    want = 0 if op == "minus" else 1
+    if psi.is_complex():
+        pr, pi = psi.real.contiguous(), psi.imag.contiguous()
+    else:
+        pr, pi = psi, None
+    ar = torch.zeros(len(s_dst), dtype=torch.float64, device=s_dst.device)
+    ai = torch.zeros_like(ar)
+    for r in range(L):
+        sel = (((s_dst >> r) & 1) == want).nonzero().flatten()         # the rows this site contributes to
+        if len(sel) == 0:
+            continue
+        part = s_dst[sel] ^ (1 << r)
+        j = part if nup_src is None else rank_t(part, L, nup_src)
+        xr = pr[j]
+        xi = torch.zeros_like(xr) if pi is None else pi[j]
+        c, s = math.cos(q * r), math.sin(q * r)
+        a, b = c * xr, s * xi
+        ar[sel] = ar[sel] + (a - b)
+        a, b = c * xi, s * xr
+        ai[sel] = ai[sel] + (a + b)
+    nf = 1.0 / math.sqrt(L)
+    return nf * ar, nf * ai
 
 
 # ---- site S^z signs ----------------------------------------------------------------------------------------------------

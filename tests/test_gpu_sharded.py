@@ -171,6 +171,103 @@ def test_sharded_fill_randn_is_sharding_independent(pkg, mode, monkeypatch):
     assert np.array_equal(got, ref)
 
 
+# ---- k_fill_randn_tiles and k_pack past their grids of 8192 blocks (a block loops over tiles / pack entries) ----
+def flat_randn(pkg, ctx, n_doubles, seed):
+    """the flat counter-based stream: element k of the first n_doubles, on the device"""
+    import torch
+    x = torch.empty(n_doubles, dtype=torch.float64, device="cuda")
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    pkg.check(pkg.lib().sd_fill_randn_dev(ctx.h, x.data_ptr(), n_doubles, seed, 0), ctx.h)
+    return x
+
+
+def nan_filled(n, dtype):
+    import torch
+    x = torch.empty(n, dtype=dtype, device="cuda")
+    (torch.view_as_real(x) if x.is_complex() else x).fill_(float("nan"))
+    return x
+
+
+def test_fill_randn_in_tile_order_past_8192_tiles_unsharded(pkg, monkeypatch):
+    """L = 22, nup = 11 at 8 suffix sites: 16 172 tiles of 1..70 rows, two trips of a block's tile loop.  The plan is rebuilt when
+    the shard is set and reads SD_SUFFIX_BITS again, so the variable stays set for the whole test."""
+    import torch
+    monkeypatch.setenv("SD_SUFFIX_BITS", "8")
+    m = pkg.XXZChain(22, nup=11)
+    op = pkg.ShardedOperator(m, 0, 1)
+    lb, gb, ln = m.local_tiles()
+    assert len(lb) == 16172 and len(lb) > 8192 and ln.max() == 70 and ln.min() == 1 and m.N == 705432 and op.n_local == m.N
+    assert np.array_equal(lb, gb)
+    for dtype, per in ((torch.complex128, 2), (torch.float64, 1)):
+        x = nan_filled(m.N, dtype)
+        op.fill_randn(x, 4321)
+        flat = flat_randn(pkg, m.ctx, per * m.N, 4321)
+        got = torch.view_as_real(x).reshape(-1) if per == 2 else x
+        bad = got != flat                                                  # (a NaN left behind differs from everything)
+        assert not bool(bad.any()), (per, int(bad.sum()), bad.nonzero().flatten()[:8].tolist())
+
+
+SHARD_L, SHARD_NUP, SHARD_P, SHARD_LS = 24, 12, 4, 6         # 2^18 prefixes: every rank owns far more than 8192 tiles
+
+
+@pytest.mark.parametrize("mode,n_tiles", [("class", [67339, 51117, 51117, 67339]), ("range", [61080, 57376, 57377, 61079])])
+def test_fill_randn_in_tile_order_past_8192_tiles_sharded(pkg, mode, n_tiles, monkeypatch):
+    import torch
+    monkeypatch.setenv("SD_SUFFIX_BITS", str(SHARD_LS))
+    L, nup, P = SHARD_L, SHARD_NUP, SHARD_P
+    N, seen = None, 0
+    for r in range(P):
+        m = pkg.XXZChain(L, nup=nup)
+        op = pkg.ShardedOperator(m, r, P, mode=mode)
+        assert int(m.shard_info().n_local_tiles) == n_tiles[r] and n_tiles[r] > 8192
+        rows = torch.from_numpy(m.local_rows()).cuda()
+        assert len(rows) == op.n_local
+        if N is None:
+            N = m.N
+            flat = flat_randn(pkg, m.ctx, 2 * N, 99)
+            flat_c, flat_r = torch.view_as_complex(flat.view(-1, 2)), flat[:N]
+        for dtype, ref in ((torch.complex128, flat_c), (torch.float64, flat_r)):
+            x = nan_filled(op.n_local, dtype)
+            op.fill_randn(x, 99)
+            want = ref[rows]
+            bad = (torch.view_as_real(x) != torch.view_as_real(want)).any(dim=1) if x.is_complex() else x != want
+            assert not bool(bad.any()), (mode, r, str(dtype), int(bad.sum()), bad.nonzero().flatten()[:8].tolist())
+        seen += op.n_local
+    assert seen == N
+
+
+def test_pack_past_8192_entries_and_the_apply_that_consumes_it(pkg, monkeypatch):
+    """Popcount-cell ownership with the packed send buffer at 6 suffix sites: pack lists of 16 285 / 18 595 / 18 595 / 16 285
+    entries, two to three trips of a block's entry loop.  Every entry must land where the list says; then the sharded apply at
+    this plan, which consumes the packed buffer, against the unsharded one."""
+    import torch
+    monkeypatch.setenv("SD_SUFFIX_BITS", str(SHARD_LS))
+    monkeypatch.setenv("SD_SHARD_PACK", "1")
+    L, nup, P = SHARD_L, SHARD_NUP, SHARD_P
+    for r, n_pack in enumerate([16285, 18595, 18595, 16285]):
+        m = pkg.XXZChain(L, nup=nup)
+        op = pkg.ShardedOperator(m, r, P, mode="class")
+        src, dst, ln = m.pack_list()
+        assert op.packed and int(m.shard_info().packed) == 1 and len(src) == n_pack and n_pack > 8192
+        assert (ln > 0).all() and (src >= 0).all() and (src + ln <= op.n_local).all() and (dst >= 0).all() and (dst + ln <= op.n_send).all()
+        within = np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln, ln)         # 0 .. len-1 inside every entry
+        si = torch.from_numpy(np.repeat(src, ln) + within).cuda()
+        di = torch.from_numpy(np.repeat(dst, ln) + within).cuda()
+        for dtype in (torch.complex128, torch.float64):
+            x = op.fill_randn(op.empty(dtype, "cuda"), 7 + r)
+            send = op.sendbuf(x)
+            (torch.view_as_real(send) if send.is_complex() else send).fill_(float("nan"))
+            assert op.pack(x) is send
+            torch.cuda.synchronize()
+            a, b = send[di], x[si]
+            bad = (torch.view_as_real(a) != torch.view_as_real(b)).any(dim=1) if x.is_complex() else a != b
+            assert not bool(bad.any()), (r, str(dtype), int(bad.sum()), bad.nonzero().flatten()[:8].tolist())
+            if int(ln.sum()) == op.n_send:                                            # the list covers the buffer: no NaN may remain
+                assert not bool(torch.isnan(torch.view_as_real(send) if send.is_complex() else send).any())
+        assert int(ln.sum()) == op.n_send
+    check_virtual_shards(pkg, L, nup, P, "class", {})
+
+
 def test_sharded_kpm_driver_matches_oracle(pkg, O, monkeypatch):
     """config 5 in miniature (driver logic with one rank; the multi-rank exchange is covered above): S(q,w) via the
     sharded KPM driver == the oracle within BASELINE's 1e-8."""

@@ -1,6 +1,7 @@
-"""The yardstick of tests/test_gpu_operator_grids.py, proven without a GPU: the row restatements of tests/rows_ref.py (torch, run
-here on the CPU) against the numpy restatement of tests/typicality_ref.py -- itself proven against Kronecker products by
-tests/test_typicality_host.py -- and the two ports of the combinadic order against each other."""
+"""The yardstick of tests/test_gpu_operator_grids.py and tests/test_gpu_transverse_grids.py, proven without a GPU: the row
+restatements of tests/rows_ref.py (torch, run here on the CPU) against the numpy restatement of tests/typicality_ref.py -- itself
+proven against Kronecker products by tests/test_typicality_host.py -- S^-+_q against tests/transverse_ref.py, and the two ports
+of the combinadic order against each other."""
 from math import comb
 
 import numpy as np
@@ -8,6 +9,7 @@ import pytest
 import torch
 
 import rows_ref as RR
+import transverse_ref as T
 import typicality_ref as R
 
 
@@ -104,6 +106,31 @@ def test_szq_rows_and_site_signs_against_the_numpy_restatement(L, nup):
     szs = np.array([R.sz_site(states, i) for i in range(1, L + 1)])
     for r in range(L):
         assert np.array_equal(RR.lag_sums_t(s, L, r).numpy(), np.sum(szs * np.roll(szs, -r, axis=0), axis=0))
+
+
+@pytest.mark.parametrize("L,nup", [(10, 5), (10, 1), (10, 9), (10, None), (13, 6)])
+@pytest.mark.parametrize("op", ["minus", "plus"])
+def test_spm_rows_equal_the_numpy_restatement_bit_for_bit(L, nup, op):
+    """`spm_rows_t` against tests/transverse_ref.py: the two share the definition only (another rank, another way of skipping
+    the rows a site does not reach), so they are held to equality.  nup = 1 -> 0 and nup = L - 1 -> L are one-row targets."""
+    N = (1 << L) if nup is None else comb(L, nup)
+    nup_dst = None if nup is None else nup + (-1 if op == "minus" else 1)
+    n_dst = (1 << L) if nup is None else comb(L, nup_dst)
+    rng = np.random.default_rng(100 * L + (nup or 0))
+    real = rng.standard_normal(N)
+    cplx = rng.standard_normal(N) + 1j * rng.standard_normal(N)
+    s_dst = RR.configurations_t(torch.arange(n_dst, dtype=torch.int64), L, nup_dst)
+    if nup is not None:
+        assert np.array_equal(s_dst.numpy(), T.sector_states(L, nup_dst))
+    top = 0.0
+    for psi in (real, cplx):
+        for q in (0.0, 0.3, 2 * np.pi * 3 / L):
+            want = T.spm(L, nup, psi, q, op)
+            re, im = RR.spm_rows_t(torch.from_numpy(psi), s_dst, L, nup, q, op)
+            assert re.dtype == torch.float64 and re.shape == (n_dst,) and im.shape == (n_dst,)
+            assert np.array_equal(re.numpy(), want.real) and np.array_equal(im.numpy(), want.imag), (L, nup, op, q)
+            top = max(top, np.abs(want).max())
+    assert top > 0.1                                                       # a real comparison, not zeros against zeros
 
 
 def test_popcount_of_wide_configurations():
