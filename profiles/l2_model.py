@@ -9,10 +9,14 @@ flight; a tile's reads are spread evenly over its lifetime.  The L2 is modelled 
 usage: python profiles/l2_model.py [L] [order ...]      orders: lex chunk orbit greedy ... block<B>c<C>[d]
   block<B>c<C>: block orbits (csrc/orbit_key.hpp through its restatement profiles/orbit_key.py) with the leading B four-site
                 blocks eligible and a capacity of C tenths of a bit; block0c60 is orbit6.  A trailing d deals every orbit to the
-                queue with the fewest rows so far instead of round-robin.  Rows per queue are printed for every orbit order.
+                queue with the fewest rows so far instead of round-robin; d:<cost> deals by another cost of csrc/xcd_deal.hpp
+                (profiles/orbit_key.py: rows slots req out, or mix:<w_a>:<cost_a>:<w_b>:<cost_b>), in runs of n orbits with a
+                trailing :run<n>, e.g. block2c78d:slots or block2c78d:slots:run3.
+                Rows, slots and packed blocks per queue are printed for every orbit order.
 environment: LS, CAP_MIB, W (tiles in flight per XCD), LO / HI (tile lengths simulated; LO=1 HI=1024: the packed launch),
   ASC=1 (tiles enumerated by ascending base row, the order in which sd_build_plan hands them to xcd_queues, instead of
-  ascending prefix integer), MALL_MIB.
+  ascending prefix integer), MALL_MIB, CLOCK (two-level model, MALL_MIB > 0: a tile starts at its index in its queue, the
+  default, or at the cumulative rows / slots / req / out of its queue before it -- the clock the queues are assumed to follow).
 The packed launch at L=32 as the planner orders it, four workgroups (128 tiles) per CU in flight:
   ASC=1 LO=1 HI=1024 W=128 python profiles/l2_model.py 32 orbit6 block2c78 block2c78d block5c72 block5c72d
 """
@@ -22,7 +26,7 @@ from collections import OrderedDict
 from math import comb
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from orbit_key import orbit_key  # noqa: E402
+from orbit_key import cost_of, deal, orbit_key, parse_cost, tile_costs  # noqa: E402
 
 L = int(sys.argv[1]) if len(sys.argv) > 1 else 28
 orders = sys.argv[2:] or ["lex", "chunk", "orbit"]
@@ -73,7 +77,7 @@ def canon(P, FO, greedy):
     return C0, member
 
 
-def order_orbit(tiles, FO=6, greedy=False, OC=1, gray=False, block=None, deal_rows=False):
+def order_orbit(tiles, FO=6, greedy=False, OC=1, gray=False, block=None, deal_rows=False, deal_cost=None, run=1):
     first, keys = {}, []
     for P in tiles:
         if block:
@@ -89,11 +93,27 @@ def order_orbit(tiles, FO=6, greedy=False, OC=1, gray=False, block=None, deal_ro
     q = [[] for _ in range(8)]
     rows = [0] * 8
     o, k, largest = 0, 0, 0
+    dealt = None
+    if deal_cost is not None:                                          # the dealing of csrc/xcd_deal.hpp, restated in orbit_key.py
+        orbits, k2 = [], 0
+        while k2 < len(idx):
+            e = k2
+            while e < len(idx) and keys[idx[e]][0] == keys[idx[k2]][0]:
+                e += 1
+            c = [e - k2, 0, 0, 0, 0]
+            for i in idx[k2:e]:
+                for n, v in enumerate(tile_costs(tiles[i], p, LS, nup, block[0], block[1])):
+                    c[1 + n] += v
+            orbits.append(tuple(c))
+            k2 = e
+        dealt = deal(orbits, deal_cost, run)
     while k < len(idx):
         e = k
         while e < len(idx) and keys[idx[e]][0] == keys[idx[k]][0]:
             e += 1
         x = rows.index(min(rows)) if deal_rows else (o // OC) % 8      # fewest rows so far, ties to the lowest queue index
+        if dealt is not None:
+            x = dealt[o]
         q[x].extend(tiles[i] for i in idx[k:e])
         rows[x] += sum(tile_len(tiles[i]) for i in idx[k:e])
         largest = max(largest, e - k)
@@ -101,7 +121,22 @@ def order_orbit(tiles, FO=6, greedy=False, OC=1, gray=False, block=None, deal_ro
         k = e
     print(f"  orbits {o}  largest {largest} tiles  rows per queue {rows}"
           f"  max - min {(max(rows) - min(rows)) / (sum(rows) / 8) * 100:.3f} % of the mean")
+    slots = [sum((tile_len(P) + 255) // 256 for P in x) for x in q]
+    blocks = [packed_blocks(x) for x in q]
+    print(f"  rows per queue max - min {max(rows) - min(rows)}   slots per queue max - min {max(slots) - min(slots)} of {max(slots)}"
+          f"   packed blocks per queue max - min {max(blocks) - min(blocks)} of {max(blocks)}")
     return q
+
+
+def packed_blocks(queue):
+    """workgroups of four 256-row wave slots that sd_build_plan packs a queue into (next fit, a tile never split)"""
+    n, used = 0, 4
+    for P in queue:
+        s_ = (tile_len(P) + 255) // 256
+        if used + s_ > 4:
+            n, used = n + 1, 0
+        used += s_
+    return n
 
 
 def order_chunk(tiles, CH=32):
@@ -115,11 +150,19 @@ def order_lex(tiles):
     return [tiles[x::8] for x in range(8)]
 
 
+CLOCK = os.environ.get("CLOCK", "index")
+CLOCK_UNIT = [1.0]          # mean cost of a tile over all queues (set by simulate_all), so that W tiles are in flight on average
+
+
 def events(queue):
     ev = []
     life = 1.0
+    cum = 0
     for j, P in enumerate(queue):
         t0 = j * life / W
+        if CLOCK != "index":
+            t0 = cum / CLOCK_UNIT[0] * life / W
+            cum += tile_costs(P, p, LS, nup, *ORBIT_OF_CLOCK)[("rows", "slots", "req", "out").index(CLOCK)]
         reads = [((P, 0), n_up_first(P) * 16), ((P, 1), (tile_len(P) - n_up_first(P)) * 16)]
         for b in range(1, p):
             if ((P >> (b - 1)) ^ (P >> b)) & 1:
@@ -171,6 +214,9 @@ def simulate(queue):
 def simulate_all(queues, mall_bytes):
     """all eight XCDs with private L2s in front of one shared memory-side cache -> (requested, L2 misses, MALL misses)"""
     ev = []
+    if CLOCK != "index":
+        k = ("rows", "slots", "req", "out").index(CLOCK)
+        CLOCK_UNIT[0] = sum(tile_costs(P, p, LS, nup, *ORBIT_OF_CLOCK)[k] for q in queues for P in q) / sum(len(q) for q in queues)
     for x, q in enumerate(queues):
         ev.extend((t, x, obj, sz) for (t, obj, sz) in events(q))
     ev.sort(key=lambda e: e[0])
@@ -187,15 +233,24 @@ def simulate_all(queues, mall_bytes):
     return req, m2, m3
 
 
+ORBIT_OF_CLOCK = [0, 60]     # (eligible blocks, capacity) of the order being simulated: the 'out' clock needs the orbits
+
+
 def parse(name):
     if name == "lex":
         return order_lex(all_tiles)
     if name.startswith("chunk"):
         return order_chunk(all_tiles, int(name[5:] or 32))
     if name.startswith("block"):
-        deal = name.endswith("d")
+        name, _, cost = name.partition(":")
+        run = 1
+        if cost.rpartition(":")[2].startswith("run"):             # block2c78d:slots:run3: runs of three orbits per queue
+            cost, _, r_ = cost.rpartition(":")
+            run = int(r_[3:])
+        by_rows = name.endswith("d") and not cost
         B_, C_ = name[5:].rstrip("d").split("c")
-        return order_orbit(all_tiles, block=(int(B_), int(C_)), deal_rows=deal)
+        ORBIT_OF_CLOCK[:] = [int(B_), int(C_)]
+        return order_orbit(all_tiles, block=(int(B_), int(C_)), deal_rows=by_rows, deal_cost=parse_cost(cost) if cost else None, run=run)
     if name.startswith("orbit") or name.startswith("greedy") or name.startswith("gray"):
         kind = "greedy" if name.startswith("greedy") else ("gray" if name.startswith("gray") else "orbit")
         rest = name[len(kind):]

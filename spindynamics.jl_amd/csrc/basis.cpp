@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "orbit_key.hpp"
+#include "xcd_deal.hpp"
 #include "sd_internal.hpp"
 
 int64_t sd_binom(int n, int k) {
@@ -150,24 +151,59 @@ static int count_nn_hops(const sd_model *m) {
 // Block orbits (profiles/ablation_block_orbits.md): odd-pair orbits never close the even bonds (2,3), (4,5), .. in L2, and 56 % of
 // the tiles have too few flippable pairs to fill 2^6.  The packed launch builds its orbits from the leading SD_ORBIT_QUAD_BLOCKS
 // four-site blocks (all configurations of a block with the same filling: its three bonds close inside the orbit) up to a capacity
-// of SD_ORBIT_CAP_TENTHS / 10 bits, and deals every orbit to the queue with the fewest rows so far (SD_ORBIT_DEAL_ROWS), ties to
+// of SD_ORBIT_CAP_TENTHS / 10 bits, and deals the orbits to the least-loaded queue (first by rows; now by slots, in runs: below), ties to
 // the lowest queue index.  Orbits now hold up to 192 tiles (216 with more blocks), and dealt round-robin they leave the eight queues 5-10 % apart in rows:
 // every block order was then SLOWER than odd pairs (L=32: 10.19-11.09 ms against 10.22), at 4, 5 and 6 workgroups per CU alike.
 // Dealt by rows (queues within 0.02 %) they win: L=32 10.51 -> 10.04 ms, L=30 2.45 -> 2.31; odd pairs dealt by rows gain 0.9 %.
 // (2 blocks, 7.8 bits) is the default; 6.2 bits loses 3 % to it, 7.2 bits 0.3 %, 3 blocks at 8.2 bits is 0.2 % faster at L=32 and
-// 1 % slower at L=30; five or six workgroups per CU (SD_PACK_WGS_PER_CU) gain nothing.  0 blocks, 60, no row dealing is the old table.
+// 1 % slower at L=30; five or six workgroups per CU (SD_PACK_WGS_PER_CU) gain nothing.
+// What to deal by (xcd_deal.hpp; profiles/ablation_queue_clock.md): per-block time stamps of the launch (SD_PACK_TRACE) show block i on
+// XCD (i + 7) % 8 without exception, and the XCDs, dealt by rows, 1 000 blocks apart in queue position but only 24 orbits (about 110
+// blocks, one in-flight window) apart in the orbit sequence: every balanced dealing keeps them in step.  No host-computable cost is the
+// queues' clock (1 000-block windows: requested bytes leave 5-7 % residual, rows 7-8 %, slots 9 %, slots + requested bytes 3-5 %).
+// Dealt by wave SLOTS the queues end 6 blocks apart instead of 1 422 and are 16 orbits apart: -0.6 % at L=32; requested bytes,
+// out-of-orbit bytes and the fitted mix lie between rows and slots; round-robin is +4.6 %.  RUNS of consecutive orbits on one queue,
+// which lost under round-robin dealing, win once the dealing is balanced (sequence neighbours share out-of-orbit partners: L2 hit
+// rate 0.488 -> 0.505, fabric-side bytes -3.4 %): 2 / 3 / 4 / 6 / 8 orbits -0.5 / -0.9 / -0.9 / -0.9 / -0.5 % on top of slots, also
+// -1.2 % under rows.  Default: slots, runs of 3 (L=32 10.009 -> 9.855 ms, L=30 -1.2...1.5 %, L=28 -1.2 %); at slot dealing 8.2 bits,
+// 3 blocks and five workgroups per CU are within +-0.3 % and were not kept.  SD_ORBIT_DEAL_COST=1 SD_ORBIT_RUN=1 is the table dealt by
+// rows; 0 blocks, 60, cost 0 the one before it.
 #ifndef SD_ORBIT_QUAD_BLOCKS
 #define SD_ORBIT_QUAD_BLOCKS 2
 #endif
 #ifndef SD_ORBIT_CAP_TENTHS
 #define SD_ORBIT_CAP_TENTHS 78
 #endif
-#ifndef SD_ORBIT_DEAL_ROWS
-#define SD_ORBIT_DEAL_ROWS 1
+#ifdef SD_ORBIT_DEAL_ROWS
+#error "SD_ORBIT_DEAL_ROWS is gone: -DSD_ORBIT_DEAL_COST=0 (round-robin) or 1 (rows), see xcd_deal.hpp"
+#endif
+#ifndef SD_ORBIT_DEAL_COST
+#define SD_ORBIT_DEAL_COST 2          // sd_deal_cost: 0 round-robin, 1 rows, 2 slots, 3 requested bytes, 4 out-of-orbit bytes, 5 mix
+#endif
+#ifndef SD_ORBIT_DEAL_MIX_A
+#define SD_ORBIT_DEAL_MIX_A 1         // mix: SD_ORBIT_DEAL_W_A * cost MIX_A + SD_ORBIT_DEAL_W_B * cost MIX_B
+#endif
+#ifndef SD_ORBIT_DEAL_MIX_B
+#define SD_ORBIT_DEAL_MIX_B 2
+#endif
+#ifndef SD_ORBIT_DEAL_W_A
+#define SD_ORBIT_DEAL_W_A 1
+#endif
+#ifndef SD_ORBIT_DEAL_W_B
+#define SD_ORBIT_DEAL_W_B 1
+#endif
+#ifndef SD_ORBIT_RUN
+#define SD_ORBIT_RUN 3                // consecutive orbits dealt as one (runs of orbits per queue)
 #endif
 static_assert(SD_ORBIT_QUAD_BLOCKS >= 0 && SD_ORBIT_CAP_TENTHS >= 0 && SD_ORBIT_CAP_TENTHS <= 150, "orbit member ids take 16 key bits");
-struct OrbitRule { int quad_blocks, cap_tenths; bool deal_rows; };
-static const OrbitRule XCD_RULE_CLASSES = {0, 50, false}, XCD_RULE_PACKED = {SD_ORBIT_QUAD_BLOCKS, SD_ORBIT_CAP_TENTHS, SD_ORBIT_DEAL_ROWS != 0};
+static_assert(SD_ORBIT_DEAL_COST >= SD_DEAL_ROUND_ROBIN && SD_ORBIT_DEAL_COST <= SD_DEAL_MIX, "dealing cost: sd_deal_cost");
+static_assert(SD_ORBIT_DEAL_MIX_A >= SD_DEAL_ROWS && SD_ORBIT_DEAL_MIX_A <= SD_DEAL_OUT_BYTES && SD_ORBIT_DEAL_MIX_B >= SD_DEAL_ROWS &&
+              SD_ORBIT_DEAL_MIX_B <= SD_DEAL_OUT_BYTES && SD_ORBIT_DEAL_W_A >= 0 && SD_ORBIT_DEAL_W_B >= 0, "mix of two single costs, weights >= 0");
+static_assert(SD_ORBIT_RUN >= 1, "orbits per run");
+struct OrbitRule { int quad_blocks, cap_tenths; sd_deal_rule deal; };
+static const OrbitRule XCD_RULE_CLASSES = {0, 50, {SD_DEAL_ROUND_ROBIN, SD_DEAL_ROWS, SD_DEAL_ROWS, 0, 0, 1}},
+                       XCD_RULE_PACKED = {SD_ORBIT_QUAD_BLOCKS, SD_ORBIT_CAP_TENTHS,
+                                          {SD_ORBIT_DEAL_COST, SD_ORBIT_DEAL_MIX_A, SD_ORBIT_DEAL_MIX_B, SD_ORBIT_DEAL_W_A, SD_ORBIT_DEAL_W_B, SD_ORBIT_RUN}};
 static std::vector<std::vector<size_t>> xcd_queues(const sd_model *m, int p, const std::vector<uint32_t> &tp_io,
                                                    std::vector<int64_t> &first_seen, const OrbitRule rule) {
   std::vector<std::vector<size_t>> q(8);
@@ -200,22 +236,27 @@ static std::vector<std::vector<size_t>> xcd_queues(const sd_model *m, int p, con
       std::vector<size_t> idx(nt);
       for (size_t k = 0; k < nt; ++k) idx[k] = k;
       std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
-      // deal whole orbits to the 8 XCD queues: round-robin, or (deal_rows) to the queue with the fewest rows so far, ties to the
-      // lowest queue index
-      size_t o = 0;
-      int64_t q_rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      // deal whole orbits, or runs of consecutive orbits, to the 8 XCD queues: round-robin, or to the queue with the lowest cost
+      // so far, ties to the lowest queue index (xcd_deal.hpp)
+      std::vector<sd_deal_orbit> orb;
+      std::vector<size_t> orb_end;                               // orbit o = sorted positions orb_end[o-1] .. orb_end[o]
+      const bool with_bytes = sd_deal_needs_bytes(rule.deal);
       for (size_t k = 0; k < nt;) {
         size_t e = k;
         while (e < nt && (key[idx[e]] >> 16) == (key[idx[k]] >> 16)) ++e;
-        size_t x = o % 8;
-        if (rule.deal_rows) {
-          x = 0;
-          for (size_t y = 1; y < 8; ++y) if (q_rows[y] < q_rows[x]) x = y;
+        orb.push_back(sd_deal_orbit{0, 0, 0, 0, 0}); orb_end.push_back(e);
+        for (size_t t = k; t < e; ++t) {
+          const uint32_t P = tp_io[idx[t]];
+          const int t2 = m->nup - __builtin_popcount(P);         // suffix filling; the straddling bond hops the rows whose first suffix site differs from site p
+          sd_deal_add_tile(orb.back(), P, p, B(m, m->LS, t2), ((P >> (p - 1)) & 1u) ? B(m, m->LS - 1, t2) : B(m, m->LS - 1, t2 - 1),
+                           rule.quad_blocks, rule.cap_tenths, with_bytes);
         }
-        for (size_t t = k; t < e; ++t) q[x].push_back(idx[t]);
-        q_rows[x] += (int64_t)(e - k) * B(m, m->LS, m->nup - __builtin_popcount(tp_io[idx[k]]));   // members have equal length
-        ++o; k = e;
+        k = e;
       }
+      std::vector<uint8_t> orb_q(orb.size());
+      sd_xcd_deal(orb.data(), orb.size(), rule.deal, orb_q.data());
+      for (size_t o = 0, k = 0; o < orb.size(); k = orb_end[o++])
+        for (size_t t = k; t < orb_end[o]; ++t) q[orb_q[o]].push_back(idx[t]);
       for (size_t k = 0; k < nt; ++k) first_seen_reset(tp_io[k]);
     } else {
       // runs of CH consecutive tiles per queue (long lists), or the list as it is (block b = tile b: queue b % 8)
@@ -900,6 +941,9 @@ int sd_build_plan(sd_model *m, int rank, int nranks, std::string &err) {
           used += ns_t;
         }
       }
+#if SD_PACK_TRACE
+      for (int x = 0; x < 8; ++x) m->pack_q_blocks[x] = (int64_t)(qb[x].size() / 4);
+#endif
       size_t longest = 0;
       for (auto &v : qb) longest = std::max(longest, v.size() / 4);
       for (size_t j = 0; j < longest; ++j)
@@ -1128,6 +1172,11 @@ int sd_upload_model(sd_model *m, std::string &err) {
     if (!m->blk_tiles.empty() && d.suf_part && d.wrap_hop < 0 && d.n_gen == 0) {
       if ((rc = up(m, m->blk_tiles, &d.blk_tiles, err))) return rc;
       d.n_blk = (int)(m->blk_tiles.size() / 4);
+#if SD_PACK_TRACE
+      const uint64_t *tr = nullptr;
+      if ((rc = up(m, std::vector<uint64_t>((size_t)3 * (size_t)d.n_blk, 0), &tr, err))) return rc;
+      d.pack_trace = const_cast<uint64_t *>(tr);
+#endif
     }
   }
   // General couplings (no exact shortcut for the diagonal): the reference's sequential sum of up to 2L-1 rounded terms per
@@ -1156,3 +1205,22 @@ int sd_upload_model(sd_model *m, std::string &err) {
   m->dev_ready = true;
   return SD_OK;
 }
+
+#if SD_PACK_TRACE
+// Measurement builds only (profiles/pack_trace.py): the records of the last packed launch and, per wave slot of the block table,
+// the prefix of its tile (0xFFFFFFFF: idle), and the blocks of each queue.  rec: 3 * n_blk words, slot_prefix: 4 * n_blk,
+// q_blocks: 8.  Returns n_blk, or -1.
+extern "C" int64_t sd_pack_trace_read(const sd_model *m, uint64_t *rec, uint32_t *slot_prefix, int64_t *q_blocks) {
+  if (!m || !m->dev_ready || m->dm.n_blk <= 0 || !m->dm.pack_trace) return -1;
+  const size_t nb = (size_t)m->dm.n_blk;
+  if (rec) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpy(rec, m->dm.pack_trace, 3 * nb * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  }
+  if (q_blocks)
+    for (int x = 0; x < 8; ++x) q_blocks[x] = m->pack_q_blocks[x];
+  if (slot_prefix)
+    for (size_t k = 0; k < 4 * nb; ++k) slot_prefix[k] = m->blk_tiles[k] < 0 ? 0xFFFFFFFFu : m->single_prefix[(size_t)m->blk_tiles[k]];
+  return (int64_t)nb;
+}
+#endif

@@ -106,6 +106,10 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   constexpr int WR = R * 64;                                   // rows of a wave
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   static_assert(!PACK || (PK && !GEN && R == 4 && BLOCK == 256), "packed launch: four slots of 256 rows, packed tables, chain bonds");
+#if SD_PACK_TRACE
+  uint64_t trace_t0 = 0;
+  if constexpr (PACK) trace_t0 = wall_clock64();
+#endif
   constexpr int SLOT_ROWS = WR + 1;                            // PACK: LDS rows of a wave slot (its own zero row + 256 rows)
   V *tile = reinterpret_cast<V *>(smem);                       // row 0: all zero; rows 1..len: the tile's psi
   int *lbin = reinterpret_cast<int *>(smem + (size_t)(max_len + 1) * sizeof(V));   // !PK only
@@ -658,6 +662,19 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
       if (tid == 0) { partials[2 * (size_t)tix] = a; partials[2 * (size_t)tix + 1] = b; }
     }
   }
+#if SD_PACK_TRACE
+  if constexpr (PACK) {
+    // lane 0 of wave 0, plain vector stores: entry clock, clock once this wave's stores have left (vmcnt 0), XCC id (bits 3:0 of
+    // hardware register 20).  blockIdx.y = 0 only: the buffer holds one record per block of a single-vector launch.
+    if (dm.pack_trace && tid == 0 && blockIdx.y == 0) {
+      __builtin_amdgcn_s_waitcnt(0);
+      uint64_t *rec_t = dm.pack_trace + 3 * (size_t)blockIdx.x;
+      rec_t[0] = trace_t0;
+      rec_t[1] = wall_clock64();
+      rec_t[2] = (uint64_t)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u);
+    }
+  }
+#endif
 }
 
 // =====================================================================

@@ -31,6 +31,9 @@
 #define SD_MAX_BONDS 4096  // bond lists are uploaded to device memory; this bounds host validation only
 #define SD_MAX_PREFIX_BITS 26
 #define SD_FS_MAX_RANKS 8   // full-basis sharding: ranks = top index bits, nranks in {2, 4, 8}
+#ifndef SD_PACK_TRACE
+#define SD_PACK_TRACE 0     // 1: per-block time stamps of the packed launch (measurement builds only, see sd_dev_model::pack_trace)
+#endif
 
 // everything a workgroup needs to start on a tile, fetched with one scalar load
 struct sd_tile_rec {
@@ -168,6 +171,12 @@ struct sd_dev_model {
   // -1 (idle); a tile of len rows holds ceil(len / 256) consecutive slots of one record.  n_blk = 0: no table, one launch per class.
   int n_blk;
   const int32_t *blk_tiles;
+#if SD_PACK_TRACE
+  // Trace form of the packed launch (profiles/build_variant.sh with -DSD_PACK_TRACE=1 compiles EVERY source with it: the field
+  // changes this struct; profiles/pack_trace.py): three words per block -- wall clock (100 MHz) at entry, after the last store,
+  // and the XCC id.  Every launch overwrites the records of the one before.
+  uint64_t *pack_trace;
+#endif
 };
 
 #define SD_N_LEN_CLASS 5   // tile length classes: workgroups of 64, 128, 256, 512, 1024 threads (x 4 rows)
@@ -216,6 +225,9 @@ struct sd_model {
   std::vector<int64_t> single_base;
   std::vector<sd_tile_rec> single_rec;
   std::vector<int32_t> blk_tiles;              // block table of the packed launch (see sd_dev_model), 4 entries per block; empty: none
+#if SD_PACK_TRACE
+  int64_t pack_q_blocks[8] = {0};              // blocks of each XCD queue in blk_tiles (block j of queue x is block 8j + x while all queues last)
+#endif
   int max_tile_len = 0;        // longest OWNED tile
   int max_tile_len_all = 0;    // longest tile of the whole basis (a partner tile imported from a peer may be longer than any owned one)
   bool hop_pow2 = false;  // every NN hop amplitude is +-2^k (or 0): J*psi is exact, fma == mul+add
