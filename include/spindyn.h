@@ -546,6 +546,53 @@ int sd_opstring_expect(sd_ctx *ctx, const sd_model *m, int dtype, const void *br
                        const sd_opterm *terms, int n_terms, double *out);
 int sd_opstring_expect_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_dev, const void *ket_dev, int64_t n,
                            const sd_opterm *terms, int n_terms, double *out);
+/* ---- S^z-basis statistics: participation moments, counting statistics, projective snapshots -------------------------------------
+ * Everything here reads the weights w_s = |psi_s|^2 of the basis configurations s (site i is bit i - 1) in one streaming pass over
+ * psi.  Nothing is divided by <psi|psi>.  Rows are in the basis order of sd_model_states, so "row r" means the same on every plan.
+ * Fixed-nup sectors and the full basis; unsharded models only.
+ *
+ * sd_basis_moments: out (host, 5 + nq doubles) = sum_s w_s, sum_s w_s ln w_s (a term is 0 where w_s = 0), max_s w_s, the lowest row
+ *   that attains the maximum (stored as a double, exact below 2^53), a reserved 0, then sum_s w_s^q for the nq exponents of `q`
+ *   (0 .. SD_MOMENT_MAX_Q host doubles, each finite, > 0 and != 1: q = 1 is the Shannon term above).  q = 2, 3, 4 are formed by
+ *   multiplication, other exponents by pow.  The maximum is compared as (w, -row) pairs, so ties go to the lowest row whatever the
+ *   order of the comparisons.
+ * sd_counting_range: host only (works on a model created without a context).  The values popcount(s & mask) takes on the basis:
+ *   *m_min .. *m_min + *n_bins - 1.  In a sector, with a = popcount(mask): max(0, nup - (L - a)) .. min(a, nup); in the full basis
+ *   0 .. a.  SD_EARG for a mask bit at or above L or a NULL pointer.
+ * sd_counting_statistics: P_out (host, K (L + 1) doubles, every entry written) with P_out[k (L + 1) + m] = sum_s w_s [popcount(s &
+ *   masks[k]) = m], m = 0 .. L, for the K masks (1 .. SD_COUNT_MAX_MASKS host uint64) of `masks`: the distribution of the number of
+ *   up spins in subsystem k.  Bins outside a mask's range (sd_counting_range) are exact zeros.  A mask with more than
+ *   SD_COUNT_MAX_BINS reachable values is SD_EARG (full basis, a subsystem of 33 or more sites).  All masks in one pass over psi.
+ * sd_sample_uniforms_host: host only.  u_out[i] = the uniform of shot first + i of stream `seed`,
+ *   (double)(mix64((seed ^ SALT) ^ mix64(k)) >> 11) * 2^-53 in [0, 1), mix64 the hash of the normal stream (sd_fill_randn_host) and SALT a
+ *   fixed constant, exact in IEEE arithmetic: host and device agree to the bit.
+ * sd_sample_configurations: `shots` rows drawn independently from w_s / sum w: rows_out[k] (host int64, may be NULL) and
+ *   configs_out[k] (host uint64, the configuration of that row), k = 0 .. shots - 1.  Shot k has the target t_k = u_k W, W the
+ *   library's own sum of the weights, and is the row at which the running sum of the weights, rows in basis order, first exceeds
+ *   t_k: the rows are cut into fixed chunks of 1024 consecutive rows, the chunk weights are scanned (monotone non-decreasing), the
+ *   chunk is found by bisection and walked in row order.  The result is a function of (psi, seed, shots) alone, not of the tile plan,
+ *   and shot k does not depend on `shots`.  Every returned row lies in [0, N) and has w > 0.  shots = 0 writes nothing.
+ * Sums in a fixed order: the same call gives the same bits.  _dev: psi is a device pointer; results go to host pointers and the call
+ * synchronises the stream.
+ * SD_EARG: an exponent <= 0, equal to 1 or not finite, nq outside 0..SD_MOMENT_MAX_Q, K outside 1..SD_COUNT_MAX_MASKS, a mask bit at or
+ * above L, a mask with too many bins, shots < 0, a NULL pointer (rows_out excepted), a dtype other than SD_F64 / SD_C128, a sharded
+ * model, a model without device tables.  SD_EDIM: n is not the basis dimension.  SD_EZERO: sd_sample_configurations of a vector
+ * whose weights sum to zero (or to something not finite).  A model with no rows gives zeros. */
+#define SD_MOMENT_MAX_Q 8
+#define SD_COUNT_MAX_MASKS 256
+#define SD_COUNT_MAX_BINS 33
+int sd_basis_moments(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const double *q, int nq, double *out);
+int sd_basis_moments_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const double *q, int nq, double *out);
+int sd_counting_range(const sd_model *m, uint64_t mask, int *m_min, int *n_bins);
+int sd_counting_statistics(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const uint64_t *masks, int K,
+                           double *P_out);
+int sd_counting_statistics_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const uint64_t *masks, int K,
+                               double *P_out);
+int sd_sample_uniforms_host(uint64_t seed, uint64_t first, int64_t n, double *u_out);
+int sd_sample_configurations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int64_t shots, uint64_t seed,
+                             int64_t *rows_out, uint64_t *configs_out);
+int sd_sample_configurations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int64_t shots,
+                                 uint64_t seed, int64_t *rows_out, uint64_t *configs_out);
 /* create_spin_operator(site, op)(psi, model)   src/Hamiltonian.jl:49-136.  site is 1-based.  S^z is diagonal and works
  * in any basis; S^+, S^-, S^x, S^y change the magnetisation and are rejected in a fixed-nup sector (SD_EARG), as the
  * reference does.  out has psi's element type; S^y needs a ComplexF64 psi (SD_EARG otherwise: the reference's

@@ -21,7 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
-       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, typicality_sample, typicality_correlation_function,
+       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -551,6 +551,66 @@ function pair_correlations(psi::AbstractVector, model::Model; component::Symbol=
     check(ccall((:sd_pair_correlations, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint, Ptr{Float64}),
                 model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), component === :pm ? 1 : 0, out), model.ctx.h)
     return permutedims(reshape(reinterpret(ComplexF64, out), model.L, model.L))     # the ABI is row-major
+end
+
+# ---- S^z-basis statistics (DESIGN.md 20): one streaming pass over w_s = |psi_s|^2 each, nothing divided by <psi|psi> ----
+# (sum w, sum w ln w, max w, its lowest row (1-based here), [sum w^q for q in qs]); at most 8 exponents, each > 0 and != 1
+function basis_moments(psi::AbstractVector, model::Model, qs::AbstractVector{<:Real}=Float64[])
+    p = hostvec(psi); q = Vector{Float64}(qs)
+    out = Vector{Float64}(undef, 5 + length(q))
+    check(ccall((:sd_basis_moments, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Float64}, Cint, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), q, length(q), out), model.ctx.h)
+    return (out[1], out[2], out[3], Int64(out[4]) + 1, out[6:end])
+end
+
+# S_q = ln(sum p^q) / (1 - q) of p = |psi_s|^2 / <psi|psi>; q = 1 the Shannon entropy, q = Inf -ln max p
+function participation_entropy(psi::AbstractVector, model::Model; q::Real=2)
+    q > 0 || throw(ArgumentError("q must be positive"))
+    W, wlnw, wmax, _, sums = basis_moments(psi, model, (q == 1 || isinf(q)) ? Float64[] : [Float64(q)])
+    q == 1 && return log(W) - wlnw / W
+    isinf(q) && return -log(wmax / W)
+    return log(sums[1] / W^q) / (1 - q)
+end
+
+site_mask(sites) = reduce(|, (UInt64(1) << (Int(i) - 1) for i in sites); init=UInt64(0))
+
+# the values popcount(s & mask) takes on the basis: (m_min, n_bins)
+function counting_range(model::Model, mask::UInt64)
+    lo = Ref{Cint}(0); nb = Ref{Cint}(0)
+    check(ccall((:sd_counting_range, libspindyn), Cint, (Ptr{Cvoid}, UInt64, Ptr{Cint}, Ptr{Cint}), model.h, mask, lo, nb), model.ctx.h)
+    return (Int(lo[]), Int(nb[]))
+end
+
+# P[k, m + 1] = probability that subsystem k (a list of 1-based sites) holds m up spins, m = 0..L; at most 256 subsystems per call
+function counting_statistics(psi::AbstractVector, model::Model, subsystems; normalize::Bool=true)
+    p = hostvec(psi); masks = UInt64[site_mask(A) for A in subsystems]
+    out = Vector{Float64}(undef, length(masks) * (model.L + 1))
+    check(ccall((:sd_counting_statistics, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{UInt64}, Cint, Ptr{Float64}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), masks, length(masks), out), model.ctx.h)
+    P = permutedims(reshape(out, model.L + 1, length(masks)))     # the ABI is row-major
+    return normalize ? P ./ sum(P[1, :]) : P
+end
+
+function number_entropy(psi::AbstractVector, model::Model, subsystem)
+    pm = filter(>(0), counting_statistics(psi, model, [subsystem])[1, :])
+    return -sum(pm .* log.(pm))
+end
+
+# the uniforms of shots first .. first + n - 1 of stream `seed` (0-based shot numbers)
+function sample_uniforms(seed::Integer, first::Integer, n::Integer)
+    u = Vector{Float64}(undef, n)
+    check(ccall((:sd_sample_uniforms_host, libspindyn), Cint, (UInt64, UInt64, Int64, Ptr{Float64}), seed, first, n, u), C_NULL)
+    return u
+end
+
+# projective snapshots: (configurations::Vector{UInt64}, rows (1-based)) drawn from |psi_s|^2 / <psi|psi>
+function sample_configurations(psi::AbstractVector, model::Model, shots::Integer; seed::Integer=0)
+    p = hostvec(psi)
+    rows = Vector{Int64}(undef, shots); cfg = Vector{UInt64}(undef, shots)
+    check(ccall((:sd_sample_configurations, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Int64, UInt64, Ptr{Int64}, Ptr{UInt64}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), shots, seed, rows, cfg), model.ctx.h)
+    return (cfg, rows .+ 1)
 end
 
 # bonds: a vector of (i, j) site pairs (1-based, i != j), or nothing for the distinct site pairs of the model's hopping list in list order

@@ -27,6 +27,9 @@ from .operators import (Term, chirality_correlations, chirality_terms, hamiltoni
                         op_string, operator_adjoint, operator_apply, operator_check, operator_expectations,
                         operator_groundstate, operator_hamiltonian, operator_is_hermitian, operator_simplify, pack_terms,
                         scalar_chirality, string_order, string_order_terms)
+from .statistics import (counting_statistics, cut_counting_statistics, inverse_participation_ratio, magnetization_cumulants,
+                         most_probable_configuration, number_entropy, participation_entropy, sample_configurations,
+                         snapshot_spins)
 from . import initial_states
 from .initial_states import domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 from .api import dynamical_structure_factor, groundstate, structure_factor, time_evolve

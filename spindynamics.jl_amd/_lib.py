@@ -150,6 +150,14 @@ PROTOTYPES = {
     "sd_current_bracket_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _dp, _dp]),
     "sd_pair_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _i, _dp]),
     "sd_pair_correlations_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _dp]),
+    "sd_basis_moments": (_i, [_vp, _vp, _i, _vp, _i64, _dp, _i, _dp]),
+    "sd_basis_moments_dev": (_i, [_vp, _vp, _i, _vp, _i64, _dp, _i, _dp]),
+    "sd_counting_range": (_i, [_vp, _u64, _ip, _ip]),
+    "sd_counting_statistics": (_i, [_vp, _vp, _i, _vp, _i64, _u64p, _i, _dp]),
+    "sd_counting_statistics_dev": (_i, [_vp, _vp, _i, _vp, _i64, _u64p, _i, _dp]),
+    "sd_sample_uniforms_host": (_i, [_u64, _u64, _i64, _dp]),
+    "sd_sample_configurations": (_i, [_vp, _vp, _i, _vp, _i64, _i64, _u64, _i64p, _u64p]),
+    "sd_sample_configurations_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i64, _u64, _i64p, _u64p]),
     "sd_bond_apply": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
     "sd_bond_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
     "sd_dimer_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _d, _d, _dp, _dp]),

@@ -9,6 +9,14 @@
 
 namespace sd_dev {
 
+// The counter-based uniform of the projective snapshots (kernels_basis_stats.hip), hashed like the normal stream's uniforms with
+// sd_mix64: u_k in [0, 1) = the top 53 bits of the hash times 2^-53, both exact in IEEE arithmetic, so host and device agree to
+// the bit.  The salt keeps the stream apart from the normal stream of the same seed.
+#define SD_SAMPLE_SALT 0x5AD5B1A5C0F1E2D3ULL
+__host__ __device__ inline double sd_sample_uniform(uint64_t seed, uint64_t k) {
+  return (double)(sd_mix64((seed ^ SD_SAMPLE_SALT) ^ sd_mix64(k)) >> 11) * (1.0 / 9007199254740992.0);
+}
+
 __host__ __device__ inline uint64_t sd_f64_bits(double d) { uint64_t b; __builtin_memcpy(&b, &d, sizeof b); return b; }
 __host__ __device__ inline double sd_bits_f64(uint64_t b) { double d; __builtin_memcpy(&d, &b, sizeof d); return d; }
 

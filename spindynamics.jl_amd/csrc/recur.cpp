@@ -1893,6 +1893,60 @@ int pair_correlations_core(sd_ctx *ctx, const sd_model *m, int dtype, const void
   return SD_OK;
 }
 
+// ---- S^z-basis statistics (kernels_basis_stats.hip) ----
+int basis_moments_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const double *q, int nq, double *out,
+                       bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!out || (nq > 0 && !q)) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (nq < 0 || nq > SD_MOMENT_MAX_Q) return sd_set_err(ctx, SD_EARG, "basis moments: between 0 and SD_MOMENT_MAX_Q exponents");
+  DBuf in, res;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
+  RC(res.alloc(ctx, 5 + SD_MOMENT_MAX_Q));
+  RC(sd_launch_basis_moments(ctx, m, dtype, p, q, nq, res.p));
+  SD_HIP(ctx, hipMemcpyAsync(out, res.p, sizeof(double) * (size_t)(5 + nq), hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+
+int counting_statistics_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const uint64_t *masks, int K,
+                             double *P_out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!P_out || !masks) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (K < 1 || K > SD_COUNT_MAX_MASKS) return sd_set_err(ctx, SD_EARG, "counting statistics: between 1 and SD_COUNT_MAX_MASKS masks");
+  DBuf in, res;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
+  const int64_t np = (int64_t)K * (m->L + 1);
+  RC(res.alloc(ctx, np));
+  RC(sd_launch_counting_statistics(ctx, m, dtype, p, masks, K, res.p));
+  SD_HIP(ctx, hipMemcpyAsync(P_out, res.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+
+int sample_configurations_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int64_t shots, uint64_t seed,
+                               int64_t *rows_out, uint64_t *configs_out, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (shots < 0) return sd_set_err(ctx, SD_EARG, "snapshots: a negative number of shots");
+  if (shots > 0 && !configs_out) return sd_set_err(ctx, SD_EARG, "null argument");
+  DBuf in, res;
+  const double *p = nullptr;
+  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
+  RC(res.alloc(ctx, 2 * std::max<int64_t>(shots, 1)));     // rows, then configurations: 8 bytes each
+  int64_t *rows_dev = (int64_t *)res.p;
+  uint64_t *cfg_dev = (uint64_t *)(res.p + std::max<int64_t>(shots, 1));
+  RC(sd_launch_sample_configurations(ctx, m, dtype, p, shots, seed, rows_dev, cfg_dev));
+  if (shots == 0) return SD_OK;
+  if (rows_out) SD_HIP(ctx, hipMemcpyAsync(rows_out, rows_dev, sizeof(int64_t) * (size_t)shots, hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipMemcpyAsync(configs_out, cfg_dev, sizeof(uint64_t) * (size_t)shots, hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+
 // the 0-based bits lo < hi of the bond of the 1-based sites (i, j): D_b is symmetric in its two sites
 int bond_bits(sd_ctx *ctx, const sd_model *m, int i, int j, int *lo, int *hi) {
   if (i < 1 || i > m->L || j < 1 || j > m->L) return sd_set_err(ctx, SD_EARG, "a bond site is outside 1..L");
@@ -2282,6 +2336,44 @@ extern "C" int sd_pair_correlations(sd_ctx *ctx, const sd_model *m, int dtype, c
 extern "C" int sd_pair_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int component,
                                         double *M_out) {
   return abi_guard(ctx, [&]() -> int { return pair_correlations_core(ctx, m, dtype, psi_dev, n, component, M_out, true); });
+}
+
+extern "C" int sd_basis_moments(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const double *q, int nq,
+                                double *out) {
+  return abi_guard(ctx, [&]() -> int { return basis_moments_core(ctx, m, dtype, psi_host, n, q, nq, out, false); });
+}
+extern "C" int sd_basis_moments_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const double *q, int nq,
+                                    double *out) {
+  return abi_guard(ctx, [&]() -> int { return basis_moments_core(ctx, m, dtype, psi_dev, n, q, nq, out, true); });
+}
+extern "C" int sd_counting_range(const sd_model *m, uint64_t mask, int *m_min, int *n_bins) {
+  if (!m || !m_min || !n_bins) return SD_EARG;
+  return sd_counting_range_host(m, mask, m_min, n_bins);
+}
+extern "C" int sd_counting_statistics(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const uint64_t *masks,
+                                      int K, double *P_out) {
+  return abi_guard(ctx, [&]() -> int { return counting_statistics_core(ctx, m, dtype, psi_host, n, masks, K, P_out, false); });
+}
+extern "C" int sd_counting_statistics_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n,
+                                          const uint64_t *masks, int K, double *P_out) {
+  return abi_guard(ctx, [&]() -> int { return counting_statistics_core(ctx, m, dtype, psi_dev, n, masks, K, P_out, true); });
+}
+extern "C" int sd_sample_uniforms_host(uint64_t seed, uint64_t first, int64_t n, double *u_out) {
+  if (!u_out || n < 0) return SD_EARG;
+  for (int64_t i = 0; i < n; ++i) u_out[i] = sd_sample_uniform_host(seed, first + (uint64_t)i);
+  return SD_OK;
+}
+extern "C" int sd_sample_configurations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int64_t shots,
+                                        uint64_t seed, int64_t *rows_out, uint64_t *configs_out) {
+  return abi_guard(ctx, [&]() -> int {
+    return sample_configurations_core(ctx, m, dtype, psi_host, n, shots, seed, rows_out, configs_out, false);
+  });
+}
+extern "C" int sd_sample_configurations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int64_t shots,
+                                            uint64_t seed, int64_t *rows_out, uint64_t *configs_out) {
+  return abi_guard(ctx, [&]() -> int {
+    return sample_configurations_core(ctx, m, dtype, psi_dev, n, shots, seed, rows_out, configs_out, true);
+  });
 }
 
 extern "C" int sd_bond_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int i, int j, double xy,

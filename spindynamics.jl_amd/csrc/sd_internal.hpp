@@ -397,6 +397,23 @@ int sd_launch_opstring(sd_ctx *ctx, const sd_model *m, int dtype, const void *ps
 int sd_launch_opstring_expect(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra, const void *ket, const sd_opgroup *groups_dev,
                               const int32_t *op_first_dev, const sd_opterm_dev *terms_dev, int n_ops, double *dst);
 
+// S^z-basis statistics (kernels_basis_stats.hip): one streaming pass over the weights w = |psi|^2 each.  Unsharded
+// models; deterministic.
+// dst (device, 5 + nq doubles) = sum w, sum w ln w, max w, the lowest row that attains it, 0, sum w^q for the exponents of q_host.
+// Queued on the context's stream.
+int sd_launch_basis_moments(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, const double *q_host, int nq, double *dst);
+// the values popcount(s & mask) takes on the basis of m: *m_min .. *m_min + *n_bins - 1 (host only); SD_EARG for a bit at or above L
+int sd_counting_range_host(const sd_model *m, uint64_t mask, int *m_min, int *n_bins);
+// P_dev (device, K (L + 1) doubles, every entry written): P[k (L + 1) + m] = sum_s w_s [popcount(s & masks_host[k]) = m].  Returns after
+// the stream has drained (its tables go back to the context's pool).
+int sd_launch_counting_statistics(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, const uint64_t *masks_host, int K,
+                                  double *P_dev);
+// rows_dev / configs_dev (device, `shots` entries each): rows drawn from w / sum w and their configurations; SD_EZERO for a zero
+// vector.  Synchronises the stream.
+int sd_launch_sample_configurations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t shots, uint64_t seed,
+                                    int64_t *rows_dev, uint64_t *configs_dev);
+double sd_sample_uniform_host(uint64_t seed, uint64_t k);   // the uniform of shot k (randn.hpp, sd_sample_uniform)
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.
