@@ -19,11 +19,11 @@ Cells (15):
                               L=23 nup=11, lanc_m=10 (k_gs_scale past its 2048 blocks)                                     1
   krylov / chebyshev / lanczos_tridiag at L=25 nup=12 (k_lanczos_fold, k_ccombine, k_cheb_init, k_ew2, k_promote)          2
 
-What this file cannot see.  At N = 705 432 only the 1024-block passes of the ground-state chain wrap (k_gs_pass, k_gs_update,
-k_gs_correct); k_gs_scale (2048 blocks of pairs) wraps from N = 1 048 577 on, which is what the L=23 cell is for; k_mdot and
-k_gemv_cols (16384 blocks) stay inside one pass at every ground-state size here.  At L=22 a single Lanczos vector takes
-k_lanczos_fold_p as well (the launch-bound form, up to 2^22 rows); the streaming k_lanczos_fold wraps in the L=25 cells.
-The recursion cells compare whole recursions at the project's bars: they show THAT a kernel is wrong, not which.
+The recursion cells compare whole recursions at the project's bars.  The vector kernels themselves -- every pass of the ground-state
+chain (k_gs_pass, k_gs_update, k_gs_correct, k_gs_scale past its 2048 blocks), k_mdot, k_gemv_cols, k_ccombine and the elementwise
+passes past their 16384 blocks -- are pinned one launcher at a time, bit for bit or under rigorous bounds, in
+tests/test_gpu_blas1_kernels.py.  At L=22 a single Lanczos vector takes k_lanczos_fold_p (the launch-bound form, up to 2^22 rows); the
+streaming k_lanczos_fold wraps in the L=25 cells.
 
 Run time: the oracle on the CPU is what these cells wait for (a few applies at 5.2 M rows, 18 Lanczos steps at 0.7 M), not the
 GPU; the shapes are the smallest that cross the caps."""
