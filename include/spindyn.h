@@ -593,6 +593,54 @@ int sd_sample_configurations(sd_ctx *ctx, const sd_model *m, int dtype, const vo
                              int64_t *rows_out, uint64_t *configs_out);
 int sd_sample_configurations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int64_t shots,
                                  uint64_t seed, int64_t *rows_out, uint64_t *configs_out);
+/* ---- entanglement across a chain cut: the blocks of the reduced density matrix as Gram matrices ---------------------------------
+ * The cut k (1 .. L-1) separates sites 1..k (part A, the low k bits of a configuration) from sites k+1..L (part B).  Write a
+ * configuration s = (P, S) with the prefix P = s & (2^k - 1) and the suffix S = s >> k.  In a fixed-nup sector psi is, without a
+ * copy, one dense matrix per number m of up spins in A:
+ *     Psi_m[a, j] = psi[off_m[a] + j],   a < dA(m) = C(k, m),   j < dB(m) = C(L - k, nup - m),
+ * off_m[a] the first row of the a-th prefix of popcount m: the rows that share a prefix are one contiguous run of the basis, the runs
+ * of one m have the same length and the same internal order.  In the full basis there is one block, reported with m = -1:
+ * Psi[a, j] = psi[j 2^k + a], dA = 2^k, dB = 2^(L-k).  The reduced density matrices are block diagonal,
+ *     side A (SD_CUT_A): G_m[a][a'] = sum_j Psi_m[a, j] conj(Psi_m[a', j])      (rho_A = (+)_m G_m, dimension d = dA),
+ *     side B (SD_CUT_B): G_m[j][j'] = sum_a Psi_m[a, j] conj(Psi_m[a, j'])      (rho_B = (+)_m G_m, dimension d = dB),
+ * and both sides of a block have the same non-zero spectrum.  SD_CUT_AUTO takes, block by block, the side of the smaller dimension
+ * (a tie goes to A).  The row order of a block is the order of first appearance in the basis: prefixes for A, suffix configurations
+ * for B; in the full basis that is the integer value.  Nothing is divided by <psi|psi>.
+ *
+ * sd_cut_blocks: host only (works on a model created without a context).  *n_blocks = the number of blocks -- m = max(0, nup - (L -
+ *   k)) .. min(k, nup) in a sector, one in the full basis -- and *n_elems = the matrix elements of the packed output, sum d^2.  With
+ *   cap >= *n_blocks the records go to `out` in ascending m: m, the side in effect, dA, dB, d and the offset (in matrix elements) of
+ *   the block in the packed output.  cap = 0: only the two counts.
+ * sd_cut_plan_info: host only.  The launch plan of (model, cut, side): *n_items work items, the largest number of pieces *max_ns the
+ *   summation range of a tile pair is cut into, and the bytes of the partial-sum workspace a call with `dtype` takes from the
+ *   context's pool.  sd_cut_plan_items: the items themselves (cap = 0: only *n_items), sd_cut_segments: the start rows of the
+ *   segments of block `block` (cap = 0: only *n_seg and *seg_len).  A segment is a run of rows with one prefix (sector; seg_len =
+ *   dB) or one suffix (full basis; seg_len = 2^k).  An item is one (block, tile row ti, tile column tj >= ti, range [k0, k1) of the
+ *   summation index) of the upper triangle of tile x tile output tiles, `slot` the offset (matrix elements) of its tile x tile
+ *   partial sums in the workspace; piece `piece` of `ns`.  form 0 (ACROSS): the Gram index counts segments, the summation index runs
+ *   inside a segment; form 1 (INSIDE): the Gram index runs inside a segment, the summation index counts segments.
+ * sd_cut_gram: G_out (host) = the blocks packed at the offsets of sd_cut_blocks, each row-major d x d: SD_C128 as (re, im) pairs,
+ *   exactly Hermitian with the diagonal's imaginary parts exactly 0; SD_F64 as d x d doubles, exactly symmetric.  Sums in a fixed
+ *   order, no atomics: the same call gives the same bits.  _dev: psi is a device pointer; G_out is a host pointer and the call
+ *   synchronises the stream.  sd_cut_gram_time_dev: the same launches on a device psi with the blocks left on the device and dropped;
+ *   *kernel_ms = the device time of the Gram kernels and the reduction alone, between two events (profiles/entanglement_bench.py).
+ * SD_EARG: a cut outside 1..L-1, a side other than the three, a dtype other than SD_F64 / SD_C128, a NULL pointer, 0 < cap < the
+ * count, a block index outside the list, a sharded model, a model without device tables (sd_cut_gram), a block with d >
+ * SD_CUT_MAX_DIM.  SD_EDIM: n is not the basis dimension.  SD_ENOMEM: the workspace does not fit; the context stays usable.  A
+ * model with no rows gives zeros. */
+#define SD_CUT_A 0
+#define SD_CUT_B 1
+#define SD_CUT_AUTO 2
+#define SD_CUT_MAX_DIM 16384
+typedef struct sd_cut_block { int32_t m, side; int64_t dA, dB, d, offset; } sd_cut_block;
+typedef struct sd_cut_item { int32_t block, ti, tj, tile, form, piece, ns, reserved; int64_t k0, k1, slot; } sd_cut_item;
+int sd_cut_blocks(const sd_model *m, int cut, int side, sd_cut_block *out, int cap, int *n_blocks, int64_t *n_elems);
+int sd_cut_plan_info(const sd_model *m, int cut, int side, int dtype, int64_t *n_items, int *max_ns, int64_t *workspace_bytes);
+int sd_cut_plan_items(const sd_model *m, int cut, int side, sd_cut_item *out, int64_t cap, int64_t *n_items);
+int sd_cut_segments(const sd_model *m, int cut, int side, int block, int64_t *starts, int64_t cap, int64_t *n_seg, int64_t *seg_len);
+int sd_cut_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int cut, int side, void *G_out);
+int sd_cut_gram_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int cut, int side, void *G_out);
+int sd_cut_gram_time_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int cut, int side, double *kernel_ms);
 /* create_spin_operator(site, op)(psi, model)   src/Hamiltonian.jl:49-136.  site is 1-based.  S^z is diagonal and works
  * in any basis; S^+, S^-, S^x, S^y change the magnetisation and are rejected in a fixed-nup sector (SD_EARG), as the
  * reference does.  out has psi's element type; S^y needs a ComplexF64 psi (SD_EARG otherwise: the reference's

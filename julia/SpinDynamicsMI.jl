@@ -21,7 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
-       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
+       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, CutBlock, cut_blocks, cut_gram, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -594,6 +594,41 @@ end
 function number_entropy(psi::AbstractVector, model::Model, subsystem)
     pm = filter(>(0), counting_statistics(psi, model, [subsystem])[1, :])
     return -sum(pm .* log.(pm))
+end
+
+# ---- entanglement across a chain cut (DESIGN.md 21): the blocks of rho_A / rho_B as Gram matrices, nothing divided by <psi|psi> ----
+struct CutBlock          # sd_cut_block
+    m::Int32             # up spins in sites 1..cut (-1: the one block of the full basis)
+    side::Int32          # 0 = A (sites 1..cut), 1 = B: the side in effect
+    dA::Int64
+    dB::Int64
+    d::Int64             # dimension of the block on that side
+    offset::Int64        # matrix elements before the block in the packed output
+end
+
+cut_side(side::Symbol) = side === :A ? Cint(0) : side === :B ? Cint(1) : side === :auto ? Cint(2) : throw(ArgumentError("side must be :A, :B or :auto"))
+
+# the blocks of the reduced density matrix across the cut between sites cut and cut + 1, and the matrix elements of all of them
+function cut_blocks(model::Model, cut::Integer; side::Symbol=:auto)
+    nb = Ref{Cint}(0); ne = Ref{Int64}(0)
+    check(ccall((:sd_cut_blocks, libspindyn), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Int64}),
+                model.h, cut, cut_side(side), C_NULL, 0, nb, ne), model.ctx.h)
+    out = Vector{CutBlock}(undef, nb[])
+    check(ccall((:sd_cut_blocks, libspindyn), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Int64}),
+                model.h, cut, cut_side(side), out, nb[], nb, ne), model.ctx.h)
+    return (out, ne[])
+end
+
+# Dict(m => G_m): side A G_m = Psi_m Psi_m' over the prefixes of popcount m, side B transpose(Psi_m) conj(Psi_m) over the suffixes,
+# rows in basis order; Hermitian (ComplexF64) or symmetric (Float64) to the bit
+function cut_gram(psi::AbstractVector, model::Model, cut::Integer; side::Symbol=:auto)
+    p = hostvec(psi)
+    blocks, ne = cut_blocks(model, cut; side=side)
+    out = Vector{eltype(p)}(undef, ne)
+    check(ccall((:sd_cut_gram, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cvoid}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), cut, cut_side(side), out), model.ctx.h)
+    # the ABI is row-major; every block equals its conjugate transpose, so the column-major reshape is conj(G_m)
+    return Dict(Int(b.m) => conj.(reshape(out[b.offset + 1:b.offset + b.d * b.d], Int(b.d), Int(b.d))) for b in blocks)
 end
 
 # the uniforms of shots first .. first + n - 1 of stream `seed` (0-based shot numbers)

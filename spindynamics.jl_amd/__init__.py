@@ -30,6 +30,9 @@ from .operators import (Term, chirality_correlations, chirality_terms, hamiltoni
 from .statistics import (counting_statistics, cut_counting_statistics, inverse_participation_ratio, magnetization_cumulants,
                          most_probable_configuration, number_entropy, participation_entropy, sample_configurations,
                          snapshot_spins)
+from .entanglement import (CutBlock, cut_blocks, cut_gram, cut_plan_info, entanglement_entropy, entanglement_profile,
+                           entanglement_spectrum, entropy_from_spectrum, reduced_density_matrix, schmidt_gap,
+                           spectrum_from_blocks, symmetry_resolved_entanglement, symmetry_resolved_from_spectrum)
 from . import initial_states
 from .initial_states import domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 from .api import dynamical_structure_factor, groundstate, structure_factor, time_evolve

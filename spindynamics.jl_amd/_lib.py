@@ -158,6 +158,13 @@ PROTOTYPES = {
     "sd_sample_uniforms_host": (_i, [_u64, _u64, _i64, _dp]),
     "sd_sample_configurations": (_i, [_vp, _vp, _i, _vp, _i64, _i64, _u64, _i64p, _u64p]),
     "sd_sample_configurations_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i64, _u64, _i64p, _u64p]),
+    "sd_cut_blocks": (_i, [_vp, _i, _i, _vp, _i, _ip, _i64p]),
+    "sd_cut_plan_info": (_i, [_vp, _i, _i, _i, _i64p, _ip, _i64p]),
+    "sd_cut_plan_items": (_i, [_vp, _i, _i, _vp, _i64, _i64p]),
+    "sd_cut_segments": (_i, [_vp, _i, _i, _i, _i64p, _i64, _i64p, _i64p]),
+    "sd_cut_gram": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _vp]),
+    "sd_cut_gram_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _vp]),
+    "sd_cut_gram_time_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _dp]),
     "sd_bond_apply": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
     "sd_bond_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
     "sd_dimer_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _d, _d, _dp, _dp]),

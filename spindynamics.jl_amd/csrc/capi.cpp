@@ -841,3 +841,139 @@ int sd_fill_randn_host(double *x, int64_t n, uint64_t seed, uint64_t first) {
 }
 
 }  // extern "C"
+
+// ---- entanglement across a chain cut (cut_plan.cpp, kernels_cut.hip) ----
+namespace {
+// no C++ exception may cross the C ABI: a failed host allocation of a plan comes back as a status
+template <class F>
+int cut_guard(sd_ctx *ctx, F &&body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc &) {
+    return sd_set_err(ctx, SD_ENOMEM, "out of host memory inside the call");
+  } catch (...) {
+    return sd_set_err(ctx, SD_EINTERNAL, "unexpected exception");
+  }
+}
+
+struct PoolTmp {   // a block of the context's pool, given back when the call returns
+  sd_ctx *ctx = nullptr;
+  void *p = nullptr;
+  size_t bytes = 0;
+  ~PoolTmp() { if (p) sd_pool_give(ctx, p, bytes); }
+  int take(sd_ctx *c, size_t want) { ctx = c; return sd_pool_take(c, want, &p, &bytes); }
+};
+
+int cut_gram_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int cut, int side, void *G_out, bool on_dev,
+                  double *kernel_ms = nullptr) {
+  if (!ctx) return SD_EARG;
+  if (!m || !psi || (!G_out && !kernel_ms)) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (!m->dev_ready) return sd_set_err(ctx, SD_EARG, "model has no device tables (created without a context)");
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  sd_cut_plan plan;
+  std::string err;
+  int rc = sd_cut_build_plan(m, cut, side, true, plan, err);
+  if (rc) return sd_set_err(ctx, rc, err);
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  const size_t el = dtype == SD_C128 ? 16 : 8, out_bytes = (size_t)plan.n_out * el;
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (m->N == 0) { if (G_out) memset(G_out, 0, out_bytes); return SD_OK; }
+  SD_HIP(ctx, hipSetDevice(ctx->device));
+  PoolTmp in, res;
+  const void *p = psi;
+  if (!on_dev) {
+    if ((rc = in.take(ctx, (size_t)n * el))) return rc;
+    if ((rc = sd_xfer_h2d(ctx, in.p, psi, (size_t)n * el))) return rc;
+    p = in.p;
+  }
+  if ((rc = res.take(ctx, out_bytes))) return rc;
+  float ms = 0.0f;
+  if ((rc = sd_launch_cut_gram(ctx, m, dtype, p, plan, (double *)res.p, kernel_ms ? &ms : nullptr))) return rc;
+  if (kernel_ms) *kernel_ms = ms;
+  return G_out ? sd_xfer_d2h(ctx, G_out, res.p, out_bytes) : SD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sd_cut_blocks(const sd_model *m, int cut, int side, sd_cut_block *out, int cap, int *n_blocks, int64_t *n_elems) {
+  if (!m || !n_blocks || !n_elems || cap < 0 || (cap > 0 && !out)) return SD_EARG;
+  return cut_guard(m->ctx, [&]() -> int {
+    std::vector<sd_cut_blk> blks;
+    std::string err;
+    int64_t total = 0;
+    const int rc = sd_cut_layout(m, cut, side, blks, &total, err);
+    if (rc) return sd_set_err(m->ctx, rc, err);
+    *n_blocks = (int)blks.size();
+    *n_elems = total;
+    if (cap == 0) return SD_OK;
+    if (cap < (int)blks.size()) return sd_set_err(m->ctx, SD_EARG, "sd_cut_blocks: cap is below the number of blocks");
+    for (size_t i = 0; i < blks.size(); ++i) out[i] = sd_cut_block{blks[i].m, blks[i].side, blks[i].dA, blks[i].dB, blks[i].d, blks[i].out_off};
+    return SD_OK;
+  });
+}
+
+int sd_cut_plan_info(const sd_model *m, int cut, int side, int dtype, int64_t *n_items, int *max_ns, int64_t *workspace_bytes) {
+  if (!m || !n_items || !max_ns || !workspace_bytes) return SD_EARG;
+  return cut_guard(m->ctx, [&]() -> int {
+    if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(m->ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+    sd_cut_plan plan;
+    std::string err;
+    const int rc = sd_cut_build_plan(m, cut, side, false, plan, err);
+    if (rc) return sd_set_err(m->ctx, rc, err);
+    *n_items = (int64_t)plan.items.size();
+    *max_ns = plan.max_ns;
+    *workspace_bytes = plan.ws_elems * (dtype == SD_C128 ? 16 : 8);
+    return SD_OK;
+  });
+}
+
+int sd_cut_plan_items(const sd_model *m, int cut, int side, sd_cut_item *out, int64_t cap, int64_t *n_items) {
+  if (!m || !n_items || cap < 0 || (cap > 0 && !out)) return SD_EARG;
+  return cut_guard(m->ctx, [&]() -> int {
+    sd_cut_plan plan;
+    std::string err;
+    const int rc = sd_cut_build_plan(m, cut, side, false, plan, err);
+    if (rc) return sd_set_err(m->ctx, rc, err);
+    *n_items = (int64_t)plan.items.size();
+    if (cap == 0) return SD_OK;
+    if (cap < *n_items) return sd_set_err(m->ctx, SD_EARG, "sd_cut_plan_items: cap is below the number of items");
+    std::copy(plan.items.begin(), plan.items.end(), out);
+    return SD_OK;
+  });
+}
+
+int sd_cut_segments(const sd_model *m, int cut, int side, int block, int64_t *starts, int64_t cap, int64_t *n_seg, int64_t *seg_len) {
+  if (!m || !n_seg || !seg_len || cap < 0 || (cap > 0 && !starts)) return SD_EARG;
+  return cut_guard(m->ctx, [&]() -> int {
+    std::vector<sd_cut_blk> blks;
+    std::string err;
+    const int rc = sd_cut_layout(m, cut, side, blks, nullptr, err);
+    if (rc) return sd_set_err(m->ctx, rc, err);
+    if (block < 0 || block >= (int)blks.size()) return sd_set_err(m->ctx, SD_EARG, "sd_cut_segments: no such block");
+    const sd_cut_blk &b = blks[(size_t)block];
+    *n_seg = b.nseg;
+    *seg_len = b.seglen;
+    if (cap == 0) return SD_OK;
+    if (cap < b.nseg) return sd_set_err(m->ctx, SD_EARG, "sd_cut_segments: cap is below the number of segments");
+    std::vector<int64_t> segs;
+    sd_cut_fill_segments(m, cut, b, segs);
+    std::copy(segs.begin(), segs.end(), starts);
+    return SD_OK;
+  });
+}
+
+int sd_cut_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int cut, int side, void *G_out) {
+  return cut_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_host, n, cut, side, G_out, false); });
+}
+
+int sd_cut_gram_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int cut, int side, void *G_out) {
+  return cut_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_dev, n, cut, side, G_out, true); });
+}
+
+int sd_cut_gram_time_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int cut, int side, double *kernel_ms) {
+  if (ctx && !kernel_ms) return sd_set_err(ctx, SD_EARG, "null argument");
+  return cut_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_dev, n, cut, side, nullptr, true, kernel_ms); });
+}
+
+}  // extern "C"

@@ -414,6 +414,48 @@ int sd_launch_sample_configurations(sd_ctx *ctx, const sd_model *m, int dtype, c
                                     int64_t *rows_dev, uint64_t *configs_dev);
 double sd_sample_uniform_host(uint64_t seed, uint64_t k);   // the uniform of shot k (randn.hpp, sd_sample_uniform)
 
+// Entanglement across a chain cut (cut_plan.cpp, kernels_cut.hip): the blocks of rho_A / rho_B as Gram matrices of
+// the matrices Psi_m that psi already is (include/spindyn.h, "entanglement across a chain cut").
+#define SD_CUT_KC 16               // summation indices of one staged chunk
+#define SD_CUT_TILE 64             // output tile of k_cut_gram; blocks with d <= SD_CUT_SMALL_TILE use that tile instead
+#define SD_CUT_SMALL_TILE 16
+#define SD_CUT_TARGET_ITEMS 2048   // the summation ranges are split until the work list is about this long
+#define SD_CUT_ACROSS 0            // Gram index over segments, summation index inside a segment
+#define SD_CUT_INSIDE 1            // Gram index inside a segment, summation index over segments
+struct sd_cut_blk {                // one block, host and device
+  int64_t seg_off;                 // its segment starts: segs[seg_off .. seg_off + nseg)
+  int64_t nseg, seglen;
+  int64_t d, K;                    // Gram dimension and summation length: (nseg, seglen) ACROSS, (seglen, nseg) INSIDE
+  int64_t out_off;                 // matrix elements before this block in the packed output
+  int64_t dA, dB;
+  int32_t form, tile, m, side;
+};
+struct sd_cut_pair {               // one tile pair of the upper triangle, for k_cut_reduce
+  int32_t block, ti, tj, ns;
+  int64_t slot;                    // workspace offset (matrix elements) of its first piece; the pieces follow tile x tile apart
+};
+struct sd_cut_plan {
+  std::vector<sd_cut_blk> blks;
+  std::vector<int64_t> segs;       // empty when built without tables
+  std::vector<sd_cut_item> items;  // grouped by launch class form * 2 + (tile == SD_CUT_TILE); a pair's pieces are consecutive
+  std::vector<sd_cut_pair> pairs;
+  int64_t class_first[5] = {0, 0, 0, 0, 0};   // items of class c: [class_first[c], class_first[c + 1])
+  int64_t n_out = 0;               // matrix elements of the packed output
+  int64_t ws_elems = 0;            // matrix elements of the workspace
+  int max_ns = 1;
+};
+// the blocks of (model, cut, side) with their forms and tiles (host only); SD_EARG with a message in `err`
+int sd_cut_layout(const sd_model *m, int cut, int side, std::vector<sd_cut_blk> &blks, int64_t *n_out, std::string &err);
+// the segment starts of one block appended to `segs` (host only)
+void sd_cut_fill_segments(const sd_model *m, int cut, const sd_cut_blk &b, std::vector<int64_t> &segs);
+// layout + work list (+ segment tables when with_segs) (host only)
+int sd_cut_build_plan(const sd_model *m, int cut, int side, bool with_segs, sd_cut_plan &plan, std::string &err);
+// G_dev (device, NC doubles per element of the packed output, every entry written) = the blocks of `plan` for psi (device, `dtype`).
+// Returns after the stream has drained (tables and workspace go back to the context's pool).  kernel_ms != null: the device time of
+// the launches alone (Gram kernels and reduction), between two events.
+int sd_launch_cut_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, const sd_cut_plan &plan, double *G_dev,
+                       float *kernel_ms = nullptr);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.
