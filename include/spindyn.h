@@ -641,6 +641,38 @@ int sd_cut_segments(const sd_model *m, int cut, int side, int block, int64_t *st
 int sd_cut_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int cut, int side, void *G_out);
 int sd_cut_gram_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int cut, int side, void *G_out);
 int sd_cut_gram_time_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int cut, int side, double *kernel_ms);
+/* ---- site permutations, and the entanglement of any set of sites ------------------------------------------------------------------
+ * A site permutation pi is given as perm[0 .. L-1]: perm[i] is the 1-based site to which the spin of site i + 1 moves, a bijection of
+ * 1..L.  U_pi |s> = |pi s>, so
+ *     (U_pi psi)[idx(s)] = psi[idx(src(s))],   bit i of src(s) = bit (perm[i] - 1) of s.
+ * perm[i] = (i + 1) mod L + 1 is the translation T, perm[i] = L - i the reflection R.  The number of up spins is preserved, so source
+ * and target are the same model; fixed-nup sectors and the full basis; unsharded models only.  Every output element is bit for bit one
+ * input element.
+ *
+ * sd_site_permute: out (n elements of psi's dtype, every row written) = U_pi psi.  out must not share a byte with psi (SD_EARG: identity
+ *   and partial overlap alike).  _dev: device pointers, queued on the context's stream.
+ * sd_site_permute_sources: host only (works on a model created without a context).  rows_out[k] = the row of psi that row start + k of
+ *   the output copies, k < count, from the same byte table the kernel builds.
+ * sd_subsystem_permutation: host only.  The permutation that brings a list of n_sites distinct sites to the front: sites[j] goes to
+ *   site j + 1, in the order given, and the remaining sites go to n_sites + 1 .. L in ascending order.  perm_out: L ints.
+ * sd_subsystem_gram: the blocks of the reduced density matrix of the listed sites (side SD_CUT_A), of the other sites (SD_CUT_B), or
+ *   block by block of the smaller of the two (SD_CUT_AUTO): psi is permuted with sd_subsystem_permutation into one n-element vector
+ *   taken from the context's pool, and the result goes through sd_cut_gram at cut = n_sites.  The block records and the packed layout of
+ *   G_out are exactly those of sd_cut_blocks(m, n_sites, side, ...), with sites[j] playing site j + 1; sums, structure and determinism
+ *   are sd_cut_gram's.  sites = 1..k in order: no copy is made and the result is sd_cut_gram's bit for bit.  _dev: psi is a device
+ *   pointer; G_out is a host pointer and the call synchronises the stream.  The copy is a second vector: where two vectors do not fit
+ *   (ComplexF64 at L = 36 on one card) the call returns SD_ENOMEM and the context stays usable.
+ * SD_EARG: perm not a bijection of 1..L, sites not distinct or outside 1..L, n_sites outside 1..L-1, rows outside the basis, a NULL
+ * pointer, a dtype other than SD_F64 / SD_C128, out sharing a byte with psi, a sharded model, a model without device tables, and what
+ * sd_cut_gram refuses at cut = n_sites.  SD_EDIM: n is not the basis dimension.  A model with no rows gives empty vectors / zeros. */
+int sd_site_permute(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *perm, void *out_host);
+int sd_site_permute_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *perm, void *out_dev);
+int sd_site_permute_sources(const sd_model *m, const int *perm, int64_t start, int64_t count, int64_t *rows_out);
+int sd_subsystem_permutation(int L, const int *sites, int n_sites, int *perm_out);
+int sd_subsystem_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *sites, int n_sites, int side,
+                      void *G_out);
+int sd_subsystem_gram_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *sites, int n_sites,
+                          int side, void *G_out);
 /* create_spin_operator(site, op)(psi, model)   src/Hamiltonian.jl:49-136.  site is 1-based.  S^z is diagonal and works
  * in any basis; S^+, S^-, S^x, S^y change the magnetisation and are rejected in a fixed-nup sector (SD_EARG), as the
  * reference does.  out has psi's element type; S^y needs a ComplexF64 psi (SD_EARG otherwise: the reference's

@@ -21,7 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
-       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, CutBlock, cut_blocks, cut_gram, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
+       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, CutBlock, cut_blocks, cut_gram, permute_sites, site_permute_sources, subsystem_permutation, subsystem_gram, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -628,6 +628,48 @@ function cut_gram(psi::AbstractVector, model::Model, cut::Integer; side::Symbol=
     check(ccall((:sd_cut_gram, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cvoid}),
                 model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), cut, cut_side(side), out), model.ctx.h)
     # the ABI is row-major; every block equals its conjugate transpose, so the column-major reshape is conj(G_m)
+    return Dict(Int(b.m) => conj.(reshape(out[b.offset + 1:b.offset + b.d * b.d], Int(b.d), Int(b.d))) for b in blocks)
+end
+
+# ---- site permutations and the entanglement of any set of sites (DESIGN.md 22) ----
+# U_pi psi: perm[i] is the site to which the spin of site i moves (1-based, a bijection of 1:L); every entry is one entry of psi
+function permute_sites(psi::AbstractVector, model::Model, perm::AbstractVector{<:Integer})
+    p = hostvec(psi)
+    out = similar(p)
+    pm = Vector{Cint}(perm)
+    length(pm) == model.L || throw(ArgumentError("perm must have L entries"))
+    check(ccall((:sd_site_permute, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cint}, Ptr{Cvoid}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), pm, out), model.ctx.h)
+    return out
+end
+
+# the row of psi (1-based) that each of the rows first .. first + count - 1 (1-based) of U_pi psi copies (host only)
+function site_permute_sources(model::Model, perm::AbstractVector{<:Integer}, first::Integer, count::Integer)
+    pm = Vector{Cint}(perm)
+    length(pm) == model.L || throw(ArgumentError("perm must have L entries"))
+    rows = Vector{Int64}(undef, count)
+    check(ccall((:sd_site_permute_sources, libspindyn), Cint, (Ptr{Cvoid}, Ptr{Cint}, Int64, Int64, Ptr{Int64}),
+                model.h, pm, first - 1, count, rows), model.ctx.h)
+    return rows .+ 1
+end
+
+# the permutation that brings sites[j] to site j, in the order given, and the other sites to length(sites)+1:L in ascending order
+function subsystem_permutation(L::Integer, sites::AbstractVector{<:Integer})
+    s = Vector{Cint}(sites)
+    out = Vector{Cint}(undef, max(L, 1))
+    check(ccall((:sd_subsystem_permutation, libspindyn), Cint, (Cint, Ptr{Cint}, Cint, Ptr{Cint}), L, s, length(s), out), C_NULL)
+    return Int.(out[1:L])
+end
+
+# Dict(m => G_m) of the listed sites: the blocks of cut_gram at cut = length(sites) with sites[j] playing site j
+function subsystem_gram(psi::AbstractVector, model::Model, sites::AbstractVector{<:Integer}; side::Symbol=:auto)
+    p = hostvec(psi)
+    s = Vector{Cint}(sites)
+    blocks, ne = cut_blocks(model, length(s); side=side)
+    out = Vector{eltype(p)}(undef, ne)
+    check(ccall((:sd_subsystem_gram, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cint}, Cint, Cint, Ptr{Cvoid}),
+                model.ctx.h, model.h, dtype_code(eltype(p)), p, length(p), s, length(s), cut_side(side), out), model.ctx.h)
     return Dict(Int(b.m) => conj.(reshape(out[b.offset + 1:b.offset + b.d * b.d], Int(b.d), Int(b.d))) for b in blocks)
 end
 

@@ -21,8 +21,9 @@ from .typicality import (chebyshev_imag_coeffs, current_expectation, dqt_sample,
 from .observables import (bond_energies, bond_operator, connected_correlations, correlation_matrix, dimer_correlation_matrix,
                           dimer_structure_factor, magnetization_per_site, model_bonds, momentum_distribution,
                           static_structure_factor, structure_factor_Sq)
-from .symmetry import (is_symmetric, lowest_level, momentum_weights, quantum_numbers, reflect, spin_flip, symmetric_operator,
-                       symmetry_apply, symmetry_combine, symmetry_overlaps, symmetry_project, translate)
+from .symmetry import (is_symmetric, lowest_level, momentum_weights, permutation_compose, permutation_inverse, permute_sites,
+                       quantum_numbers, reflect, spin_flip, subsystem_permutation, symmetric_operator, symmetry_apply,
+                       symmetry_combine, symmetry_overlaps, symmetry_project, translate)
 from .operators import (Term, chirality_correlations, chirality_terms, hamiltonian_terms, multi_spin_expectation,
                         op_string, operator_adjoint, operator_apply, operator_check, operator_expectations,
                         operator_groundstate, operator_hamiltonian, operator_is_hermitian, operator_simplify, pack_terms,
@@ -30,9 +31,11 @@ from .operators import (Term, chirality_correlations, chirality_terms, hamiltoni
 from .statistics import (counting_statistics, cut_counting_statistics, inverse_participation_ratio, magnetization_cumulants,
                          most_probable_configuration, number_entropy, participation_entropy, sample_configurations,
                          snapshot_spins)
-from .entanglement import (CutBlock, cut_blocks, cut_gram, cut_plan_info, entanglement_entropy, entanglement_profile,
-                           entanglement_spectrum, entropy_from_spectrum, reduced_density_matrix, schmidt_gap,
-                           spectrum_from_blocks, symmetry_resolved_entanglement, symmetry_resolved_from_spectrum)
+from .entanglement import (CutBlock, cut_blocks, cut_gram, cut_plan_info, dense_density_matrix, entanglement_entropy,
+                           entanglement_profile, entanglement_spectrum, entropy_from_spectrum, logarithmic_negativity,
+                           mutual_information, partial_transpose, reduced_density_matrix, schmidt_gap, spectrum_from_blocks,
+                           subsystem_density_matrix, subsystem_entropy, subsystem_gram, subsystem_spectrum,
+                           symmetry_resolved_entanglement, symmetry_resolved_from_spectrum, two_site_density_matrix)
 from . import initial_states
 from .initial_states import domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 from .api import dynamical_structure_factor, groundstate, structure_factor, time_evolve

@@ -165,6 +165,12 @@ PROTOTYPES = {
     "sd_cut_gram": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _vp]),
     "sd_cut_gram_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _vp]),
     "sd_cut_gram_time_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _dp]),
+    "sd_site_permute": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _vp]),
+    "sd_site_permute_dev": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _vp]),
+    "sd_site_permute_sources": (_i, [_vp, _ip, _i64, _i64, _i64p]),
+    "sd_subsystem_permutation": (_i, [_i, _ip, _i, _ip]),
+    "sd_subsystem_gram": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _i, _vp]),
+    "sd_subsystem_gram_dev": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _i, _vp]),
     "sd_bond_apply": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
     "sd_bond_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _d, _d, _vp]),
     "sd_dimer_correlations": (_i, [_vp, _vp, _i, _vp, _i64, _ip, _i, _d, _d, _dp, _dp]),

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "sd_internal.hpp"
+#include "site_perm.hpp"
 
 int sd_set_err(sd_ctx *ctx, int code, const std::string &msg) {
   if (ctx) ctx->err = msg;
@@ -974,6 +975,127 @@ int sd_cut_gram_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_d
 int sd_cut_gram_time_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int cut, int side, double *kernel_ms) {
   if (ctx && !kernel_ms) return sd_set_err(ctx, SD_EARG, "null argument");
   return cut_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_dev, n, cut, side, nullptr, true, kernel_ms); });
+}
+
+}  // extern "C"
+
+// ---- site permutations and the entanglement of any set of sites (site_perm.hpp, kernels_permute.hip) ----
+namespace {
+bool bytes_overlap(const void *a, const void *b, size_t n) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + n && y < x + n;
+}
+
+// what every vector call checks before anything is queued; pm receives the permutation
+int permute_args(sd_ctx *ctx, const sd_model *m, int dtype, const int *perm, sd_site_perm &pm, int *identity) {
+  if (!m->dev_ready) return sd_set_err(ctx, SD_EARG, "model has no device tables (created without a context)");
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "site permutations need an unsharded model");
+  if (!sd_site_perm_make(perm, m->L, &pm, identity)) return sd_set_err(ctx, SD_EARG, "perm must be a bijection of 1..L");
+  return SD_OK;
+}
+
+int site_permute_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const int *perm, void *out, bool on_dev) {
+  if (!ctx) return SD_EARG;
+  if (!m || !psi || !perm || !out) return sd_set_err(ctx, SD_EARG, "null argument");
+  sd_site_perm pm;
+  int rc = permute_args(ctx, m, dtype, perm, pm, nullptr);
+  if (rc) return rc;
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  const size_t bytes = (size_t)n * (dtype == SD_C128 ? 16 : 8);
+  if (bytes_overlap(out, psi, bytes)) return sd_set_err(ctx, SD_EARG, "out must not alias or overlap psi");
+  if (n == 0) return SD_OK;
+  SD_HIP(ctx, hipSetDevice(ctx->device));
+  if (on_dev) return sd_launch_site_permute(ctx, m, dtype, pm, psi, out);
+  PoolTmp in, res;
+  if ((rc = in.take(ctx, bytes)) || (rc = res.take(ctx, bytes))) return rc;
+  if ((rc = sd_xfer_h2d(ctx, in.p, psi, bytes))) return rc;
+  if ((rc = sd_launch_site_permute(ctx, m, dtype, pm, in.p, res.p))) return rc;
+  return sd_xfer_d2h(ctx, out, res.p, bytes);
+}
+
+int subsystem_perm(int L, const int *sites, int n_sites, int *perm_out) {
+  if (L < 2 || L > SD_MAX_L || !sites || !perm_out || n_sites < 1 || n_sites > L - 1) return SD_EARG;
+  uint64_t seen = 0;
+  for (int j = 0; j < n_sites; ++j) {
+    const int s = sites[j];
+    if (s < 1 || s > L || ((seen >> (s - 1)) & 1)) return SD_EARG;
+    seen |= (uint64_t)1 << (s - 1);
+    perm_out[s - 1] = j + 1;
+  }
+  int next = n_sites + 1;
+  for (int i = 0; i < L; ++i)
+    if (!((seen >> i) & 1)) perm_out[i] = next++;
+  return SD_OK;
+}
+
+int subsystem_gram_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const int *sites, int n_sites, int side,
+                        void *G_out, bool on_dev) {
+  if (!ctx) return SD_EARG;
+  if (!m || !psi || !sites || !G_out) return sd_set_err(ctx, SD_EARG, "null argument");
+  int perm[SD_MAX_L + 1];
+  if (subsystem_perm(m->L, sites, n_sites, perm))
+    return sd_set_err(ctx, SD_EARG, "the sites must be distinct, in 1..L, and 1 <= n_sites <= L - 1");
+  sd_site_perm pm;
+  int identity = 0;
+  int rc = permute_args(ctx, m, dtype, perm, pm, &identity);
+  if (rc) return rc;
+  std::vector<sd_cut_blk> blks;         // the cut's own refusals (side, block dimension) before anything is queued
+  std::string err;
+  if ((rc = sd_cut_layout(m, n_sites, side, blks, nullptr, err))) return sd_set_err(ctx, rc, err);
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (identity || n == 0) return cut_gram_core(ctx, m, dtype, psi, n, n_sites, side, G_out, on_dev);
+  SD_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)n * (dtype == SD_C128 ? 16 : 8);
+  PoolTmp in, tmp;
+  const void *p = psi;
+  if (!on_dev) {
+    if ((rc = in.take(ctx, bytes))) return rc;
+    if ((rc = sd_xfer_h2d(ctx, in.p, psi, bytes))) return rc;
+    p = in.p;
+  }
+  if ((rc = tmp.take(ctx, bytes))) return rc;
+  if ((rc = sd_launch_site_permute(ctx, m, dtype, pm, p, tmp.p))) return rc;
+  return cut_gram_core(ctx, m, dtype, tmp.p, n, n_sites, side, G_out, true);   // returns after the stream has drained
+}
+}  // namespace
+
+extern "C" {
+
+int sd_site_permute(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *perm, void *out_host) {
+  return cut_guard(ctx, [&]() -> int { return site_permute_core(ctx, m, dtype, psi_host, n, perm, out_host, false); });
+}
+
+int sd_site_permute_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *perm, void *out_dev) {
+  return cut_guard(ctx, [&]() -> int { return site_permute_core(ctx, m, dtype, psi_dev, n, perm, out_dev, true); });
+}
+
+int sd_site_permute_sources(const sd_model *m, const int *perm, int64_t start, int64_t count, int64_t *rows_out) {
+  if (!m) return SD_EARG;
+  if (!perm || start < 0 || count < 0 || start > m->N - count || (count > 0 && !rows_out))
+    return sd_set_err(m->ctx, SD_EARG, "sd_site_permute_sources: null argument or rows outside the basis");
+  return cut_guard(m->ctx, [&]() -> int {
+    sd_site_perm pm;
+    if (!sd_site_perm_make(perm, m->L, &pm, nullptr)) return sd_set_err(m->ctx, SD_EARG, "perm must be a bijection of 1..L");
+    const int ntab = (m->L + 7) / 8;
+    std::vector<uint64_t> lut((size_t)256 * ntab);
+    sd_site_perm_fill(lut.data(), pm, m->L, 0, ntab, 0, 1);
+    for (int64_t k = 0; k < count; ++k)
+      rows_out[k] = sd_rank_host(m, sd_site_perm_source(lut.data(), ntab, sd_unrank_host(m, start + k)));
+    return SD_OK;
+  });
+}
+
+int sd_subsystem_permutation(int L, const int *sites, int n_sites, int *perm_out) { return subsystem_perm(L, sites, n_sites, perm_out); }
+
+int sd_subsystem_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *sites, int n_sites, int side,
+                      void *G_out) {
+  return cut_guard(ctx, [&]() -> int { return subsystem_gram_core(ctx, m, dtype, psi_host, n, sites, n_sites, side, G_out, false); });
+}
+
+int sd_subsystem_gram_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *sites, int n_sites, int side,
+                          void *G_out) {
+  return cut_guard(ctx, [&]() -> int { return subsystem_gram_core(ctx, m, dtype, psi_dev, n, sites, n_sites, side, G_out, true); });
 }
 
 }  // extern "C"

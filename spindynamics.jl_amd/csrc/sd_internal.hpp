@@ -456,6 +456,11 @@ int sd_cut_build_plan(const sd_model *m, int cut, int side, bool with_segs, sd_c
 int sd_launch_cut_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, const sd_cut_plan &plan, double *G_dev,
                        float *kernel_ms = nullptr);
 
+// Site permutations (kernels_permute.hip, site_perm.hpp): out (device, x's dtype, every row written; must not share a
+// byte with x) = U_pi x for a validated permutation.  Unsharded models with device tables; queued on the context's stream; copies bits.
+struct sd_site_perm;
+int sd_launch_site_permute(sd_ctx *ctx, const sd_model *m, int dtype, const sd_site_perm &pm, const void *x, void *out);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.

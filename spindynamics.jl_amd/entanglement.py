@@ -89,6 +89,128 @@ def cut_gram(psi, model, cut, side="auto"):
     return {int(r["m"]): out[int(r["offset"]):int(r["offset"]) + int(r["d"]) ** 2].reshape(int(r["d"]), int(r["d"])) for r in rec}
 
 
+def _sites_arg(model, sites, what):
+    try:
+        s = [int(x) for x in sites]
+        ok = all(not isinstance(x, bool) and int(x) == x for x in sites)
+    except (TypeError, ValueError):
+        s, ok = [], False
+    if not ok or not 1 <= len(s) <= model.L - 1 or len(set(s)) != len(s) or min(s) < 1 or max(s) > model.L:
+        raise ArgumentError(f"{what}: the sites must be distinct integers in 1..L = 1..{model.L}, at least 1 and at most L - 1 of them, "
+                            f"got {sites!r}")
+    return np.ascontiguousarray(s, dtype=np.intc)
+
+
+def subsystem_gram(psi, model, sites, side="auto"):
+    """The un-normalised blocks {m: G_m} of the reduced density matrix of the listed sites (side 'A'), of the other sites ('B'), or
+    block by block of the smaller of the two ('auto') -- sd_subsystem_gram: psi is permuted so that sites[j] becomes
+    site j + 1 (one copy of psi from the context's pool) and goes through the Gram kernel of cut_gram at cut = len(sites).  Blocks,
+    keys and row order are those of cut_gram(., ., len(sites), side) with sites[j] playing site j + 1; sites = 1..k in order is
+    cut_gram(psi, model, k, side) bit for bit."""
+    s = _sites_arg(model, sites, "subsystem_gram")
+    code = _side_code(side, "subsystem_gram")
+    rec, n_el = _blocks_raw(model, len(s), code)                 # every argument is refused here, before any launch
+    if len(psi) != model.N:
+        from ._lib import DimensionMismatch
+        raise DimensionMismatch("length(psi) != the basis dimension")
+    sp = s.ctypes.data_as(_ip)
+    if _is_torch(psi):
+        _bind_torch_stream(model, psi)
+        dt = _dtype_code(psi)
+        out = np.empty(n_el, dtype=np.complex128 if dt == 2 else np.float64)
+        check(lib().sd_subsystem_gram_dev(model.ctx.h, model.h, dt, psi.data_ptr(), len(psi), sp, len(s), code, out.ctypes.data),
+              model.ctx.h)
+    else:
+        x = np.ascontiguousarray(psi)
+        if x.dtype not in (np.float64, np.complex128):
+            x = x.astype(np.complex128 if np.iscomplexobj(x) else np.float64)
+        out = np.empty(n_el, dtype=x.dtype)
+        check(lib().sd_subsystem_gram(model.ctx.h, model.h, _dtype_code(x), x.ctypes.data, len(x), sp, len(s), code, out.ctypes.data),
+              model.ctx.h)
+    return {int(r["m"]): out[int(r["offset"]):int(r["offset"]) + int(r["d"]) ** 2].reshape(int(r["d"]), int(r["d"])) for r in rec}
+
+
+def subsystem_density_matrix(psi, model, sites):
+    """rho_S of the listed sites as its blocks {m: ndarray}, normalised so that the traces of all blocks sum to 1.  The rows of block
+    m are the configurations of the listed sites with m up spins, in the basis order of the sector (len(sites), m) with sites[j]
+    playing site j + 1 (the full basis: one block, key -1, rows by the integer value, sites[j] = bit j)."""
+    G = subsystem_gram(psi, model, sites, "A")
+    tr = _total_trace(G)
+    return {m: g / tr for m, g in G.items()}
+
+
+def dense_density_matrix(blocks, n_sites):
+    """The blocks of subsystem_density_matrix (or of reduced_density_matrix(.., side='A')) as the 2^s x 2^s matrix in the
+    computational basis of the s = n_sites listed sites: index = the configuration, sites[j] = bit j.  s <= 12."""
+    import itertools
+    s = int(n_sites)
+    if not 1 <= s <= 12:
+        raise ArgumentError(f"dense_density_matrix: n_sites must be in 1..12, got {n_sites!r}")
+    first = next(iter(blocks.values()))
+    rho = np.zeros((1 << s, 1 << s), dtype=np.asarray(first).dtype)
+    for m, g in blocks.items():
+        if m == -1:
+            idx = np.arange(1 << s)
+        else:
+            idx = np.array([sum(1 << b for b in c) for c in itertools.combinations(range(s), m)], dtype=np.int64)
+        if np.shape(g) != (len(idx), len(idx)):
+            raise ArgumentError(f"dense_density_matrix: block {m} is not the side-A block of {s} sites")
+        rho[np.ix_(idx, idx)] = g
+    return rho
+
+
+def subsystem_spectrum(psi, model, sites):
+    """The eigenvalues of rho_S of the listed sites, per block: {m: descending float64 array}; they sum to 1 over all blocks.  Each
+    block is taken on its smaller side (the listed sites or the rest: both have the same non-zero eigenvalues)."""
+    return spectrum_from_blocks(subsystem_gram(psi, model, sites, "auto"))
+
+
+def subsystem_entropy(psi, model, sites, q=1):
+    """The entropy S_q of the listed sites with the rest of the system (see entropy_from_spectrum for q)"""
+    _q_list(q, "subsystem_entropy")
+    return entropy_from_spectrum(subsystem_spectrum(psi, model, sites), q)
+
+
+def _disjoint(model, A, B, what):
+    a, b = [int(x) for x in _sites_arg(model, A, what)], [int(x) for x in _sites_arg(model, B, what)]
+    if set(a) & set(b):
+        raise ArgumentError(f"{what}: A and B must be disjoint, both hold {sorted(set(a) & set(b))}")
+    return a, b
+
+
+def mutual_information(psi, model, A, B, q=1):
+    """I_q(A:B) = S_q(A) + S_q(B) - S_q(A u B) of two disjoint site lists (q = 1: the von Neumann mutual information; psi is a
+    pure state, so S(A u B) = 0 when the two lists cover the system)"""
+    a, b = _disjoint(model, A, B, "mutual_information")
+    _q_list(q, "mutual_information")
+    S_ab = subsystem_entropy(psi, model, a + b, q) if len(a) + len(b) < model.L else 0.0
+    return subsystem_entropy(psi, model, a, q) + subsystem_entropy(psi, model, b, q) - S_ab
+
+
+def partial_transpose(rho, n_a, n_b):
+    """rho^{T_B} of a dense 2^(n_a + n_b) matrix whose index is a + (b << n_a): the indices of B exchanged between bra and ket"""
+    dA, dB = 1 << n_a, 1 << n_b
+    return np.asarray(rho).reshape(dB, dA, dB, dA).transpose(2, 1, 0, 3).reshape(dA * dB, dA * dB)
+
+
+def logarithmic_negativity(psi, model, A, B):
+    """E_N = ln || rho_{A u B}^{T_B} ||_1 of two disjoint site lists.  rho_{A u B} comes from the device (subsystem_density_matrix);
+    the partial transpose and `eigvalsh` run on the host on the dense matrix, so len(A) + len(B) <= 12."""
+    a, b = _disjoint(model, A, B, "logarithmic_negativity")
+    if len(a) + len(b) > 12:
+        raise ArgumentError("logarithmic_negativity: len(A) + len(B) must be at most 12")
+    if len(a) + len(b) > model.L - 1:
+        raise ArgumentError("logarithmic_negativity: A and B together must leave at least one site out")
+    rho = dense_density_matrix(subsystem_density_matrix(psi, model, a + b), len(a) + len(b))
+    lam = np.linalg.eigvalsh(partial_transpose(rho, len(a), len(b)))
+    return math.log(float(np.abs(lam).sum())) + 0.0
+
+
+def two_site_density_matrix(psi, model, i, j):
+    """The 4 x 4 density matrix of sites i and j in the computational basis: index = bit(i) + 2 bit(j) (1 = up)"""
+    return dense_density_matrix(subsystem_density_matrix(psi, model, [i, j]), 2)
+
+
 def _total_trace(G):
     tr = sum(float(np.trace(g).real) for g in G.values())
     if not tr > 0.0:

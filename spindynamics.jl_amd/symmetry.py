@@ -105,6 +105,73 @@ def spin_flip(psi, model, out=None):
     return symmetry_apply(psi, model, flip=True, out=out)
 
 
+def _perm_arg(perm, L, what):
+    """perm as a contiguous intc array of L entries (the library checks that it is a bijection of 1..L)"""
+    p = np.asarray(perm)
+    if p.ndim != 1 or len(p) != L or not (np.issubdtype(p.dtype, np.integer) or (p == np.floor(p)).all()):
+        raise ArgumentError(f"{what}: perm must be a list of L = {L} integers, a bijection of 1..L")
+    return np.ascontiguousarray(p, dtype=np.intc)
+
+
+def permute_sites(psi, model, perm, out=None):
+    """out = U_pi psi for the site permutation perm: perm[i] is the 1-based site to which the spin of site i + 1 moves,
+    a bijection of 1..L, so (U_pi psi)[idx(s)] = psi[idx(src(s))] with bit i of src(s) = bit perm[i] - 1 of s.  A vector of psi's
+    kind and dtype, every entry bit for bit one entry of psi.  out: where to write (same kind, dtype, length; it must not share
+    memory with psi)."""
+    pm = _perm_arg(perm, model.L, "permute_sites")
+    dev = _is_torch(psi)
+    x = psi if dev else _host_vec(psi)
+    out, ocode = _out_for(x, out, np.iscomplexobj(x) if not dev else x.is_complex())
+    if ocode != _dtype_code(x):
+        raise ArgumentError("out must have psi's dtype")
+    pp = pm.ctypes.data_as(_ip)
+    if dev:
+        _bind_torch_stream(model, x)
+        check(lib().sd_site_permute_dev(model.ctx.h, model.h, ocode, x.data_ptr(), len(x), pp, out.data_ptr()), model.ctx.h)
+    else:
+        check(lib().sd_site_permute(model.ctx.h, model.h, ocode, x.ctypes.data, len(x), pp, out.ctypes.data), model.ctx.h)
+    return out
+
+
+def _bijection(p, what):
+    p = np.asarray(p, dtype=np.int64)
+    if p.ndim != 1 or len(p) < 1 or not np.array_equal(np.sort(p), np.arange(1, len(p) + 1)):
+        raise ArgumentError(f"{what}: not a bijection of 1..L")
+    return p
+
+
+def permutation_inverse(perm):
+    """the permutation q with U_q U_perm = 1: q[perm[i] - 1] = i + 1 (host only)"""
+    p = _bijection(perm, "permutation_inverse")
+    q = np.empty_like(p)
+    q[p - 1] = np.arange(1, len(p) + 1)
+    return q.astype(np.intc)
+
+
+def permutation_compose(p, q):
+    """the permutation r with U_r = U_p U_q (q acts first): r[i] = p[q[i] - 1] (host only)"""
+    p, q = _bijection(p, "permutation_compose"), _bijection(q, "permutation_compose")
+    if len(p) != len(q):
+        raise ArgumentError("permutation_compose: the two permutations have different lengths")
+    return p[q - 1].astype(np.intc)
+
+
+def subsystem_permutation(L, sites):
+    """The permutation that brings the listed sites to the front (sd_subsystem_permutation; host only): sites[j] goes to site j + 1,
+    in the order given, the remaining sites to len(sites) + 1 .. L in ascending order.  The sites must be distinct, in 1..L, and
+    at least 1 and at most L - 1 of them."""
+    try:
+        s = np.ascontiguousarray([int(x) for x in sites], dtype=np.intc)
+    except (TypeError, ValueError):
+        raise ArgumentError("subsystem_permutation: sites must be a list of integers") from None
+    if any(isinstance(x, bool) or int(x) != x for x in sites) or not 1 <= int(L) <= 63:
+        raise ArgumentError("subsystem_permutation: sites must be integers and 1 <= L <= 63")
+    out = np.zeros(int(L), dtype=np.intc)
+    if lib().sd_subsystem_permutation(int(L), s.ctypes.data_as(_ip), len(s), out.ctypes.data_as(_ip)) != 0:
+        raise ArgumentError(f"subsystem_permutation: the sites must be distinct, in 1..L = 1..{int(L)}, and 1 <= len(sites) <= L - 1")
+    return out
+
+
 def symmetry_overlaps(psi, model, elements, bra=None):
     """<bra|U_g|psi> for every element of `elements` ((shift, reflect, flip) tuples, shorter tuples filled with zeros, or codes)
     from one pass over the rows -> complex128 array.  bra None: psi itself.  Sums in a fixed order: same call, same bits."""
