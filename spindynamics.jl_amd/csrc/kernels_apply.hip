@@ -80,15 +80,21 @@ namespace {
 // still occupies one wave only.  An idle slot runs as a
 // tile of no rows (every load is out of range, nothing is stored), so all four waves meet at the barriers.
 //
-// PACK, far bonds: a RING of SD_PACK_RING register sets instead of the conditional ping-pong.  One loop iteration issues the loads of
-// SD_PACK_RING consecutive entries of the far-bond list, unconditionally, and then accumulates them in list order, so the compiler
-// counts the loads in flight (s_waitcnt vmcnt(n > 0) before all but the last accumulation of an iteration).  The list is closed
-// to a multiple of the ring depth by EMPTY bonds: zero records on a valid base, J = 0 -- every lane reads 0, nothing leaves the CU,
-// and acc + J * 0 is what rows outside the straddle window do anyway.  Order and arithmetic are those of the ping-pong.
-// SD_PACK_WGS_PER_CU: workgroups of the packed launch per CU, capped through its dynamic LDS request (sd_launch_apply); 6 is what
-// the registers allow, i.e. no cap.  Fewer tiles in flight per XCD keep an orbit's partner lines in L2 until the mates re-read them;
-// the ring is what makes that affordable (the ping-pong LOSES at four workgroups, the ring gains 2 %).  Both are compile-time
-// constants with a -D override for profiles/build_variant.sh; the sweep is profiles/ablation_packed_pipeline.md.
+// PACK, far bonds: a ROLLING RING of SD_PACK_RING = D register sets instead of the conditional ping-pong.  The first D entries of
+// the far-bond list go out before the barrier; from then on D sets are in flight, in list order, and a step waits for the oldest
+// set only (s_waitcnt vmcnt((D-1)*4 + 3) down to (D-1)*4, never 0), accumulates it and issues the next entry into the same
+// registers.  The loop is unrolled by D; the rem = (nf - D) mod D entries left over run as HEAD steps before it, on sets D-rem..D-1,
+// where the prologue has put the list's first entries (entry e uses set (e + D - rem) mod D); after the loop the sets are drained
+// in order 0..D-1 with counts that fall to 0.  The compiler counts every wait.
+// Only a list SHORTER than D (an idle slot, a model without hops: no entry at all) is closed by EMPTY bonds, in the prologue: zero
+// records on a valid base, J = 0 -- every lane reads 0, nothing leaves the CU, and acc + J * 0 is what rows outside the straddle
+// window do anyway.  Order and arithmetic are those of the ping-pong.  (Until profiles/ablation_packed_rolling.md the ring issued
+// D entries and then accumulated D, draining to vmcnt(0) once per iteration, and closed EVERY list to a multiple of D.)
+// SD_PACK_WGS_PER_CU: workgroups of the packed launch per CU, capped through its dynamic LDS request (sd_launch_apply) and handed to
+// __launch_bounds__ as the waves per SIMD the registers must allow (a workgroup is one wave per SIMD).  Fewer tiles in flight per
+// XCD keep an orbit's partner lines in L2 until the mates re-read them; the ring is what makes that affordable (the ping-pong LOSES
+// at four workgroups, the ring gains 2 %).  Both are compile-time constants with a -D override for profiles/build_variant.sh; the
+// sweeps are profiles/ablation_packed_pipeline.md and profiles/ablation_packed_rolling.md.
 #ifndef SD_PACK_RING
 #define SD_PACK_RING 2
 #endif
@@ -96,9 +102,9 @@ namespace {
 #define SD_PACK_WGS_PER_CU 4
 #endif
 static_assert(SD_PACK_RING >= 2 && SD_PACK_RING <= 4, "ring depth of the packed launch: 2..4 register sets");
-static_assert(SD_PACK_WGS_PER_CU >= 2 && SD_PACK_WGS_PER_CU <= 6, "workgroups per CU of the packed launch: 2..6");
+static_assert(SD_PACK_WGS_PER_CU >= 2 && SD_PACK_WGS_PER_CU <= 5, "workgroups per CU of the packed launch: 2..5 (95 registers at D = 2)");
 template <int NC, int R, int BLOCK, bool FMA, bool PK, bool GEN = false, bool PACK = false>
-__global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_tiled(sd_dev_model dm, double *__restrict__ out_,
+__global__ __launch_bounds__(BLOCK, (GEN ? 5 : PACK ? SD_PACK_WGS_PER_CU : NC == 2 ? 4 : 5)) void k_apply_tiled(sd_dev_model dm, double *__restrict__ out_,
                                                        const double *__restrict__ psi_, int epi, sd_epi_args ea,
                                                        double *__restrict__ partials, int max_len) {
   using V = typename VT<NC>::type;
@@ -250,11 +256,13 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   uint64_t mk = fmask;
   bool have_a = false;
   auto next_lane = [&](uint64_t &m_) { const int ln = __builtin_ctzll(m_); m_ &= m_ - 1; return ln; };   // ascending bond order
-  // PACK: the ring.  Sets 0 and 1 are va and vb, the others vx; entry k of an iteration uses set k.
+  // PACK: the ring.  Its D register sets hold the rows as loaded, 16 bytes each, and are taken apart into doubles only where they
+  // are accumulated: a set that passes a join of the control flow as two doubles per row is no longer one register tuple to the
+  // compiler, which then copies it to where the other path has it -- behind a wait for the loads that define it.
   constexpr int D = PACK ? SD_PACK_RING : 2;
-  V vx[D > 2 ? D - 2 : 1][R];
+  u4 rq[D][R];
   FarBond fr[D];
-  int ring_iters = 0;
+  int ring_full = 0, ring_rem = 0;
   auto ring_next = [&]() {                                       // the next list entry, or an EMPTY bond once the list is used up
     FarBond fb;
     const bool e = mk == 0;
@@ -267,19 +275,53 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
     fb.lo = st ? st_lo : 0; fb.n = e ? 0 : st ? st_n : len;
     return fb;
   };
-  auto ring_issue = [&](const FarBond &fb, V(&v)[R]) {           // (unsharded plans only: no halo)
+  auto ring_issue = [&](const FarBond &fb, u4(&v)[R]) {          // (unsharded plans only: no halo)
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(psi + fb.base, (uint32_t)fb.n * ES);
     const uint32_t rel = off0 - (uint32_t)fb.lo * ES;
 #pragma unroll
-    for (int r = 0; r < R; ++r) buf_load(v[r], rs, rel + (uint32_t)(r * 64) * ES);
+    for (int r = 0; r < R; ++r) v[r] = __builtin_amdgcn_raw_buffer_load_b128(rs, rel + (uint32_t)(r * 64) * ES, 0, 0);
+  };
+  // The packed partner table of the suffix bonds, 4 registers per row (an L2 / L1 hit).  PACK: requested ahead of the ring's
+  // prologue; the class launches: after the stream phase (why: at the call there).
+  auto request_table = [&]() {
+    if (PK && (PACK || nn > 0)) {                                 // (PACK: always issued, so that it can be counted; no hops: no range)
+      const __amdgpu_buffer_rsrc_t rp = make_rsrc(dm.suf_part + 4 * (size_t)rec.suf_off, nn > 0 ? (uint32_t)len * 16u : 0u);
+#pragma unroll
+      for (int r = 0; r < R; ++r) pt[PK ? r : 0] = __builtin_amdgcn_raw_buffer_load_b128(rp, (uint32_t)i0 * 16u + (uint32_t)(r * 64) * 16u, 0, 0);
+    }
+  };
+  // The cached diagonal of general couplings.  PACK: requested AHEAD of the ring's prologue -- the wait for it before the barrier
+  // then leaves the D sets in flight (behind them it is a wait for everything, on every model: the compiler counts for all paths).
+  double dd[R];
+  auto load_dd = [&]() {
+    const __amdgpu_buffer_rsrc_t rd = make_rsrc(dm.diag_cache + base, (uint32_t)len * (uint32_t)sizeof(double));
+#pragma unroll
+    for (int r = 0; r < R; ++r) buf_load(dd[r], rd, (uint32_t)i0 * (uint32_t)sizeof(double) + (uint32_t)(r * 64) * (uint32_t)sizeof(double));
   };
   if constexpr (PACK) {
-    // iterations of the ring: the list length rounded up to whole rings, one at least (an idle slot, a model without hops:
-    // EMPTY bonds only), so that the first entry always goes out here, before the barrier
+    if (dm.diag_cache) load_dd();
+    request_table();
+    // the prologue of the ring: the first D entries go out here, before the barrier (they need far_base and scalars only).  A list
+    // of fewer than D entries (an idle slot, a model without hops: none at all) is closed by EMPTY bonds, here and nowhere else
+    // The list is PHASED so that the left-over entries run at its head: entry e uses set (e + D - rem) mod D.  The sets are still
+    // issued in the order 0..D-1, one straight line for every rem (a scalar select of the descriptor; a switch into D prologues
+    // makes the compiler lose count of what is in flight), so the entries of a prologue go out rotated -- which costs nothing, they
+    // leave back to back.
     const int nf = __popcll(fmask);
-    ring_iters = nf > D ? (nf + D - 1) / D : 1;
-    fr[0] = ring_next();
-    ring_issue(fr[0], va);
+    const int ring_more = nf > D ? nf - D : 0;                   // entries beyond the D of the prologue: full * D + rem
+    ring_full = ring_more / D;
+    ring_rem = ring_more - ring_full * D;
+    FarBond fe[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) fe[j] = ring_next();
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      fr[k] = fe[k];                                              // set k: entry (k + rem) mod D
+#pragma unroll
+      for (int t = 1; t < D; ++t)
+        if (ring_rem == t) fr[k] = fe[(k + t) % D];
+      ring_issue(fr[k], rq[k]);
+    }
   } else {
     if (mk) { fa = get_bond(next_lane(mk)); issue(fa, va); have_a = true; }
   }
@@ -287,10 +329,7 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   // ---- diagonal (needs own) ----
   V acc[R];
   if (dm.diag_cache) {                                         // general couplings: the diagonal was summed once per model
-    double dd[R];
-    const __amdgpu_buffer_rsrc_t rd = make_rsrc(dm.diag_cache + base, (uint32_t)len * (uint32_t)sizeof(double));
-#pragma unroll
-    for (int r = 0; r < R; ++r) buf_load(dd[r], rd, (uint32_t)i0 * (uint32_t)sizeof(double) + (uint32_t)(r * 64) * (uint32_t)sizeof(double));
+    if constexpr (!PACK) load_dd();
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = vscale(dd[r], own[r]);
   } else if (!need_sig) {
@@ -337,26 +376,41 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
   // always issued, EMPTY bonds at the end -- were measured and lose or tie for the class launches: profiles/ablation_r03.md
   // section 3.  The packed form takes the first of them, see SD_PACK_RING above.)
   if constexpr (PACK) {
-    // the first iteration (its entry 0 is in flight since before the barrier), then whole iterations: issue D, accumulate D
+    // Rolling ring.  D sets are in flight, in list order, since the prologue.  A step waits for the OLDEST set only, accumulates it
+    // and issues the next list entry into that same set.  First the rem head steps, on sets D-rem..D-1 (where the prologue put the
+    // list's first entries); from then on set 0 is the oldest: `full` loop iterations of D steps (unrolled, so a set is always the
+    // same registers), then the D sets drained in order.  There is no EMPTY bond on this path: a list of nf >= D entries costs nf
+    // bonds of loads.  (The form with the left-over steps in D tails BEHIND the loop compiles to a full drain at the loop's exit,
+    // with the sets copied to other registers: profiles/ablation_packed_rolling.md section 2.)
+    auto ring_acc = [&](int k) {
 #pragma unroll
-    for (int k = 1; k < D; ++k) { fr[k] = ring_next(); ring_issue(fr[k], k == 1 ? vb : vx[k > 2 ? k - 2 : 0]); }
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      V(&v)[R] = k == 0 ? va : k == 1 ? vb : vx[k > 2 ? k - 2 : 0];
-#pragma unroll
-      for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fr[k].J, v[r]);
-    }
-#pragma nounroll
-    for (int it = 1; it < ring_iters; ++it) {
-#pragma unroll
-      for (int k = 0; k < D; ++k) { fr[k] = ring_next(); ring_issue(fr[k], k == 0 ? va : k == 1 ? vb : vx[k > 2 ? k - 2 : 0]); }
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        V(&v)[R] = k == 0 ? va : k == 1 ? vb : vx[k > 2 ? k - 2 : 0];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fr[k].J, v[r]);
+      for (int r = 0; r < R; ++r) {
+        const u4 q = rq[k][r];
+        V v;
+        if constexpr (NC == 2) { v.x = __hiloint2double((int)q.y, (int)q.x); v.y = __hiloint2double((int)q.w, (int)q.z); }
+        acc[r] = accum<FMA>(acc[r], fr[k].J, v);
       }
+    };
+    auto ring_step = [&](int k) {                                 // (the list is not used up: no EMPTY case)
+      const FarBond nb = get_bond(next_lane(mk));                 // (scalar work: free to move into the wait)
+      ring_acc(k);
+      __builtin_amdgcn_sched_barrier(0);                          // (an issue hoisted over the accumulation needs a second set of registers)
+      fr[k] = nb;
+      ring_issue(fr[k], rq[k]);
+      // nothing moves across the end of a step: left to itself the scheduler gathers the D issues of an unrolled iteration behind
+      // its D accumulations, which is the drain to vmcnt(0) once per iteration again
+      __builtin_amdgcn_sched_barrier(0);
+    };
+#pragma unroll
+    for (int k = 1; k < D; ++k)
+      if (ring_rem >= D - k) ring_step(k);
+#pragma nounroll
+    for (int it = 0; it < ring_full; ++it) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) ring_step(k);
     }
+#pragma unroll
+    for (int k = 0; k < D; ++k) ring_acc(k);
   } else {
     while (have_a) {
       bool have_b = false;
@@ -370,13 +424,12 @@ __global__ __launch_bounds__(BLOCK, (GEN ? 5 : NC == 2 ? 4 : 5)) void k_apply_ti
       for (int r = 0; r < R; ++r) acc[r] = accum<FMA>(acc[r], fbb.J, vb[r]);
     }
   }
-  // The packed partner table of the suffix bonds is requested only now: its 4 registers per row would otherwise be live
-  // across the stream phase and cost a wave per SIMD (89 instead of 74 VGPRs for ComplexF64).  An L2 / L1 hit.
-  if (PK && nn > 0) {
-    const __amdgpu_buffer_rsrc_t rp = make_rsrc(dm.suf_part + 4 * (size_t)rec.suf_off, (uint32_t)len * 16u);
-#pragma unroll
-    for (int r = 0; r < R; ++r) pt[PK ? r : 0] = __builtin_amdgcn_raw_buffer_load_b128(rp, (uint32_t)i0 * 16u + (uint32_t)(r * 64) * 16u, 0, 0);
-  }
+  // The class launches request the packed partner table only now: its 4 registers per row would otherwise be live across the
+  // stream phase and cost them a wave per SIMD (89 instead of 74 VGPRs for ComplexF64 at six waves).  That holds for them only:
+  // the packed launch runs SD_PACK_WGS_PER_CU = 4 waves per SIMD, a budget of 128 registers of which it fills 95 WITH the table
+  // held across the ring, so its request goes out ahead of the ring's prologue and the round trip is over long before the suffix
+  // phase (-0.04 ms at L=32 against a request between the last issue and the drain: profiles/ablation_packed_rolling.md section 3).
+  if constexpr (!PACK) request_table();
   // Wrap bond (the first general bond, one site in the prefix and one in the suffix: the periodic chain's (L, 1)).  Its partner
   // rows are scattered over the whole of ONE tile, P ^ (1 << wrap_pb) -- as a per-row gather every fetched line is half used and the
   // address unit pays per line (+19 % on the apply).  The partner tile is streamed instead, coalesced like a far bond, into a
