@@ -199,6 +199,10 @@ SHIM_PROTOTYPES = {
     "b1_imag_count": (_i, [_vp, _dp, _i64, _i]),
     "b1_dot_to": (_i, [_vp, _i, _dp, _dp, _i64, _dp]),
     "b1_nrm2sq_to": (_i, [_vp, _dp, _i64, _dp]),
+    "b1_lanczos_fold": (_i, [_vp, _dp, _dp, _dp, _i64, _i, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "b1_lanczos_fold_p": (_i, [_vp, _dp, _dp, _dp, _i64, _i, _i64, _i, _dp, _i, _dp, _dp, _i, _dp, _dp, _i64, _dp, _i]),
+    "b1_lanczos_fold_scalars_p": (_i, [_vp, _i, _i, _dp, _i, _dp, _i, _dp, _dp, _i64]),
+    "b1_lanczos_fold_scalars": (_i, [_vp, _i, _dp, _dp, _dp, _dp]),
 }
 
 

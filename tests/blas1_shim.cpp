@@ -1,4 +1,4 @@
-// Test shim: reaches the vector-kernel launchers of csrc/kernels_blas1.hip from ctypes.  The launchers are ordinary C++
+// Test shim: reaches the vector-kernel and Lanczos-fold launchers of csrc/kernels_blas1.hip from ctypes.  The launchers are ordinary C++
 // functions of libspindyn.so (declared in csrc/sd_internal.hpp, default visibility, not in include/spindyn.h); this unit
 // forward-declares the ones it needs -- prototypes copied from sd_internal.hpp -- and wraps each in an extern "C" function that
 // takes the context as void *.  It includes no HIP header.  The mangled names carry the parameter types, so a prototype that
@@ -29,6 +29,15 @@ int sd_k_dotu(sd_ctx *ctx, const double *x, const double *y, int64_t N, int slot
 int sd_k_imag_count(sd_ctx *ctx, const double *xc, int64_t N, int slot);
 int sd_k_dot_to(sd_ctx *ctx, int nc, const double *x, const double *y, int64_t N, double *dst_dev);
 int sd_k_nrm2sq_to(sd_ctx *ctx, const double *x, int64_t n, double *dst_dev);
+int sd_k_lanczos_fold(sd_ctx *ctx, double *t, const double *uc, const double *up, int64_t N, int form, const double *dot_dev,
+                      const double *n2c_dev, const double *n2p_dev, double *store_alpha, double *store_bc, double *n2_out);
+int sd_k_lanczos_fold_p(sd_ctx *ctx, double *t, const double *uc, const double *up, int64_t N, int batch, int64_t bstride, int form,
+                        const double *dotp, int ndot, const double *n2cp, const double *n2pp, int nn2, double *store_alpha,
+                        double *store_bc, int64_t store_stride, double *n2out, int nb);
+int sd_k_lanczos_fold_scalars_p(sd_ctx *ctx, int batch, int form, const double *dotp, int ndot, const double *n2cp, int nn2,
+                                double *store_alpha, double *store_bc, int64_t store_stride);
+int sd_k_lanczos_fold_scalars(sd_ctx *ctx, int form, const double *dot_dev, const double *n2c_dev, double *store_alpha,
+                              double *store_bc);
 
 extern "C" {
 
@@ -90,6 +99,24 @@ int b1_dot_to(void *ctx, int nc, const double *x, const double *y, int64_t N, do
 }
 int b1_nrm2sq_to(void *ctx, const double *x, int64_t n, double *dst_dev) {
   return sd_k_nrm2sq_to(static_cast<sd_ctx *>(ctx), x, n, dst_dev);
+}
+int b1_lanczos_fold(void *ctx, double *t, const double *uc, const double *up, int64_t N, int form, const double *dot_dev,
+                    const double *n2c_dev, const double *n2p_dev, double *store_alpha, double *store_bc, double *n2_out) {
+  return sd_k_lanczos_fold(static_cast<sd_ctx *>(ctx), t, uc, up, N, form, dot_dev, n2c_dev, n2p_dev, store_alpha, store_bc, n2_out);
+}
+int b1_lanczos_fold_p(void *ctx, double *t, const double *uc, const double *up, int64_t N, int batch, int64_t bstride, int form,
+                      const double *dotp, int ndot, const double *n2cp, const double *n2pp, int nn2, double *store_alpha,
+                      double *store_bc, int64_t store_stride, double *n2out, int nb) {
+  return sd_k_lanczos_fold_p(static_cast<sd_ctx *>(ctx), t, uc, up, N, batch, bstride, form, dotp, ndot, n2cp, n2pp, nn2, store_alpha,
+                             store_bc, store_stride, n2out, nb);
+}
+int b1_lanczos_fold_scalars_p(void *ctx, int batch, int form, const double *dotp, int ndot, const double *n2cp, int nn2,
+                              double *store_alpha, double *store_bc, int64_t store_stride) {
+  return sd_k_lanczos_fold_scalars_p(static_cast<sd_ctx *>(ctx), batch, form, dotp, ndot, n2cp, nn2, store_alpha, store_bc,
+                                     store_stride);
+}
+int b1_lanczos_fold_scalars(void *ctx, int form, const double *dot_dev, const double *n2c_dev, double *store_alpha, double *store_bc) {
+  return sd_k_lanczos_fold_scalars(static_cast<sd_ctx *>(ctx), form, dot_dev, n2c_dev, store_alpha, store_bc);
 }
 
 }  // extern "C"

@@ -22,7 +22,9 @@ Cells (15):
 The recursion cells compare whole recursions at the project's bars.  The vector kernels themselves -- every pass of the ground-state
 chain (k_gs_pass, k_gs_update, k_gs_correct, k_gs_scale past its 2048 blocks), k_mdot, k_gemv_cols, k_ccombine and the elementwise
 passes past their 16384 blocks -- are pinned one launcher at a time, bit for bit or under rigorous bounds, in
-tests/test_gpu_blas1_kernels.py.  At L=22 a single Lanczos vector takes k_lanczos_fold_p (the launch-bound form, up to 2^22 rows); the
+tests/test_gpu_blas1_kernels.py; the fold family (sd_k_lanczos_fold, sd_k_lanczos_fold_p and the two kernels that file the last
+step's scalars: all twelve update kernels, every branch of the paired streaming loop, every list length and batch layout) likewise in
+tests/test_gpu_fold_kernels.py.  At L=22 a single Lanczos vector takes k_lanczos_fold_p (the launch-bound form, up to 2^22 rows); the
 streaming k_lanczos_fold wraps in the L=25 cells.
 
 Run time: the oracle on the CPU is what these cells wait for (a few applies at 5.2 M rows, 18 Lanczos steps at 0.7 M), not the
