@@ -194,6 +194,64 @@ int sd_energy_bounds(sd_ctx *ctx, const sd_model *m, int lanc_m,
 int sd_lanczos_groundstate(sd_ctx *ctx, const sd_model *m, int lanc_m, double tol, double orth_tol,
                            const double *psi0_host /* or NULL */, uint64_t seed,
                            double *E0, double *psi_gs_host /* n doubles */, int *m_actual);
+/* The lowest nev eigenpairs by thick-restart Lanczos (Wu and Simon) in bounded memory: basis_size + 1 device vectors of `dtype`
+ * (not in the reference, which stops at the ground state).
+ *   Lanczos with full re-orthogonalisation (classical Gram-Schmidt applied twice, in blocks of 8 columns) fills basis_size columns;
+ *   the projected matrix -- arrowhead plus tridiagonal after a restart -- is solved with sd_sym_eig; the lowest `keep` Ritz vectors
+ *   of the active block are formed in place by one rotation (sd_basis_rotate_dev) and the residual direction follows them.
+ *   keep = (pairs still wanted) + buffer, buffer = a third of the free columns, at least 2 and at most 8; keep <= 32.
+ *   Ritz pair i is converged when |beta_m Z[m-1, i]| <= tol * scale, scale = the largest |theta| seen so far; converged pairs are
+ *   locked from the bottom up: their columns stay in the basis as deflation and are not rotated again.
+ *   Breakdown (beta <= 1e-12 * scale): the block is an invariant subspace and its pairs are exact; while pairs are missing and fewer
+ *   than n columns are locked the solver goes on from a fresh seeded random vector orthogonalised twice against the locked columns.
+ *   confirm != 0: a single start vector holds one direction per eigenspace, so once nev pairs are locked a new sequence starts from
+ *   a fresh seeded random vector orthogonal to the locked set and runs until its lowest Ritz value has converged.  A value at or
+ *   below the nev-th level + tol * scale is locked too (a further copy of a degenerate level, or a level the first sequence missed)
+ *   and the step repeats; a value above it is reported as info->next_level (the first level above the window) and ends the call.
+ *   confirm == 0 skips this: for operators that are projectors onto a sector, which a random vector would leave.
+ * evals[nev], residuals[nev] (|H x_i - evals[i] x_i| by one apply each), evecs (n x nev column-major, of `dtype`; or NULL): the
+ * lowest min(nev, locked) pairs in ascending order; info->converged of them are valid.  max_applies (<= 0: no bound) bounds the
+ * applies of the iteration; when it is reached the pairs locked so far come back with converged < nev and status SD_OK.  The
+ * applies of the residuals are counted in info->applies on top.  dtype SD_F64 needs the built-in operator of a real model; a
+ * caller's operator (sd_ctx_set_apply_callback) may be either dtype.  The same call gives the same bits.
+ * SD_EARG (with the reason in sd_last_error): nev < 1, nev > min(n, 24), basis_size < nev + 3 while n allows more, basis_size > 128,
+ * a sharded model, NULL outputs.  basis_size is clamped to n.  SD_ENOMEM: the basis does not fit; the context stays usable.
+ * _dev: psi0 and evecs are device pointers. */
+#define SD_EIGS_MAX_BASIS 128
+#define SD_EIGS_MAX_KEEP 32
+#define SD_EIGS_MAX_NEV 24
+typedef struct sd_eigs_info {
+  int converged;            /* pairs returned (<= nev) */
+  int restarts;             /* Ritz rotations of the basis */
+  int64_t applies;          /* operator applications of the call, residuals included */
+  int basis_size;           /* after clamping to n */
+  int workspace_vectors;    /* device vectors of n elements the call held */
+  double next_level;        /* first level above the returned ones (confirm != 0 and found) */
+  int have_next_level;
+  double scale;             /* largest |Ritz value| seen: the estimate of |H| the tolerances are relative to */
+} sd_eigs_info;
+int sd_lanczos_eigenpairs(sd_ctx *ctx, const sd_model *m, int dtype, int nev, int basis_size, double tol, int64_t max_applies,
+                          int confirm, const void *psi0_host /* or NULL */, uint64_t seed, double *evals,
+                          void *evecs_host /* or NULL */, double *residuals, sd_eigs_info *info);
+int sd_lanczos_eigenpairs_dev(sd_ctx *ctx, const sd_model *m, int dtype, int nev, int basis_size, double tol, int64_t max_applies,
+                              int confirm, const void *psi0_dev /* or NULL */, uint64_t seed, double *evals,
+                              void *evecs_dev /* or NULL */, double *residuals, sd_eigs_info *info);
+/* The solver's three streaming kernels on device vectors (kernels_eigs.hip); each call synchronises the stream.
+ * sd_basis_rotate_dev: V[r, c] <- sum_{j < m} V[r, j] Q[j, c] for r < n_doubles, c < k, in place.  V: m columns of leading dimension
+ *   ld_doubles >= n_doubles; Q: real, m x k, column-major, host.  Per element the sum runs in ascending j from a zero accumulator,
+ *   one multiply then one add per term (no fused multiply-add).  Columns k..m-1 and the ld - n padding keep their bits.  A
+ *   ComplexF64 basis is rotated as 2 n doubles (Ritz coefficients of a Hermitian problem in a Lanczos basis are real).
+ *   SD_EARG unless 1 <= k <= m <= SD_EIGS_MAX_BASIS and k <= SD_EIGS_MAX_KEEP.
+ * sd_block_dots_dev: out[2c], out[2c + 1] = re, im of <V[:, c] | w> (column conjugated; im = 0 for SD_F64), c < ncols <= 8, n
+ *   elements, ld in elements, in one pass over w; summed in a fixed order.
+ * sd_block_axpy_dev: w <- w - sum_c coef[c] V[:, c], coef[c] = (coef_host[2c], coef_host[2c + 1]) (the imaginary part is ignored
+ *   for SD_F64), ascending c, one multiply and one subtraction per real term: x - cr v for real vectors,
+ *   re = (re - cr v.re) + ci v.im, im = (im - cr v.im) - ci v.re for complex ones. */
+int sd_basis_rotate_dev(sd_ctx *ctx, void *V_dev, int64_t ld_doubles, int64_t n_doubles, int m, const double *Q_host, int k);
+int sd_block_dots_dev(sd_ctx *ctx, int dtype, const void *V_dev, int64_t ld, int ncols, const void *w_dev, int64_t n,
+                      double *out_host /* 2 per column */);
+int sd_block_axpy_dev(sd_ctx *ctx, int dtype, void *w_dev, const void *V_dev, int64_t ld, int ncols, const double *coef_host,
+                      int64_t n);
 /* lanczos_tridiag   src/Lanczos.jl:196-246.  alpha_out[min(lanc_m,n)], beta_out[min(lanc_m,n)-1] */
 int sd_lanczos_tridiag(sd_ctx *ctx, const sd_model *m, const void *v_c128_host, int64_t n, int lanc_m,
                        double tol, double *alpha_out, double *beta_out, int *m_eff, double *norm_v);
@@ -696,6 +754,10 @@ int sd_initial_state_index(const sd_model *m, int kind, const int *flips, int nf
 /* ---- host utilities ------------------------------------------------------ */
 /* eigen(SymTridiagonal(d, e)): ascending eigenvalues w[n]; z (n*n column-major) may be NULL */
 int sd_symtridiag_eig(int n, const double *d, const double *e, double *w, double *z);
+/* eigen(Symmetric(A)) by cyclic Jacobi rotations, n <= 128: A is n*n (column-major; the lower triangle is read), ascending
+ * eigenvalues w[n], eigenvectors in the columns of Z (n*n column-major).  The projected matrix of a restarted Lanczos basis is
+ * arrowhead plus tridiagonal, which sd_symtridiag_eig cannot take.  SD_EARG: n outside 1..128 or a NULL pointer. */
+int sd_sym_eig(int n, const double *A, double *w, double *Z);
 /* Chebyshev expansion coefficients c_k (src/TimeEvolution/Chebyshev.jl:74-79); c_out has 2*cheb_n doubles */
 int sd_chebyshev_coeffs(int cheb_n, double a, double b, double dt, double *c_out);
 /* counter-based N(0,1) generator used for synthetic vectors: element k of the

@@ -19,7 +19,7 @@ using Random
 using Libdl
 
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
-       groundstate, time_evolve, structure_factor, dynamical_structure_factor,
+       groundstate, lowest_eigenpairs, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
        chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, CutBlock, cut_blocks, cut_gram, permute_sites, site_permute_sources, subsystem_permutation, subsystem_gram, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
@@ -246,6 +246,48 @@ function estimate_energy_bounds(model::Model; lanc_m::Int=80, seed::Union{Nothin
                 model.ctx.h, model.h, lanc_m, va === nothing ? C_NULL : va, vb === nothing ? C_NULL : vb,
                 seed === nothing ? 0 : seed, lo, hi), model.ctx.h)
     return lo[], hi[]
+end
+
+# The lowest k eigenpairs by thick-restart Lanczos in basis_size + 1 device vectors (sd_lanczos_eigenpairs; not in the reference,
+# which stops at the ground state).  Returns (E, X, info): X is N x converged, info a NamedTuple of the fields of sd_eigs_info
+# plus the residuals.  confirm=true looks for further copies of degenerate levels from fresh random vectors.
+mutable struct EigsInfo      # sd_eigs_info
+    converged::Cint
+    restarts::Cint
+    applies::Int64
+    basis_size::Cint
+    workspace_vectors::Cint
+    next_level::Float64
+    have_next_level::Cint
+    scale::Float64
+    EigsInfo() = new(0, 0, 0, 0, 0, 0.0, 0, 0.0)
+end
+
+function lowest_eigenpairs(model::Model; k::Int=4, basis_size::Union{Nothing,Int}=nothing, tol::Float64=1e-10,
+                           max_applies::Int=200000, confirm::Bool=true, psi0::Union{Nothing,Vector{Float64}}=nothing,
+                           seed::Integer=0)
+    N = length(model)
+    bs = basis_size === nothing ? min(N, max(2k + 8, 24)) : basis_size
+    E = zeros(Float64, max(k, 1)); res = zeros(Float64, max(k, 1))
+    X = zeros(Float64, N, max(k, 1))
+    info = EigsInfo()
+    check(ccall((:sd_lanczos_eigenpairs, libspindyn), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Float64, Int64, Cint, Ptr{Cvoid}, UInt64, Ptr{Float64}, Ptr{Cvoid},
+                 Ptr{Float64}, Ref{EigsInfo}),
+                model.ctx.h, model.h, dtype_code(Float64), k, bs, tol, max_applies, confirm ? 1 : 0,
+                psi0 === nothing ? C_NULL : psi0, seed, E, X, res, info), model.ctx.h)
+    nc = Int(info.converged)
+    return E[1:nc], X[:, 1:nc], (converged=nc, restarts=Int(info.restarts), applies=info.applies, basis_size=Int(info.basis_size),
+                                 workspace_vectors=Int(info.workspace_vectors), residuals=res[1:nc], scale=info.scale,
+                                 next_level=info.have_next_level != 0 ? info.next_level : nothing)
+end
+
+# eigen(Symmetric(A)) by cyclic Jacobi rotations (sd_sym_eig, n <= 128) -> (w ascending, Z)
+function sym_eig(A::Matrix{Float64})
+    n = size(A, 1)
+    w = Vector{Float64}(undef, n); Z = Matrix{Float64}(undef, n, n)
+    check(ccall((:sd_sym_eig, libspindyn), Cint, (Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), n, A, w, Z))
+    return w, Z
 end
 
 function time_evolve(model::Model, ψ0::AbstractVector, t::Real; method::Symbol=:krylov, Ebounds=nothing,

@@ -15,13 +15,14 @@ from .solvers import (chebyshev_coeffs, chebyshev_time_evolve, compute_chebyshev
                       get_kernel, get_rescaling_params, kpm_reconstruct, kpm_sqw, kpm_sqw_transverse, kpm_sw,
                       krylov_time_evolve, lanczos_extremal, lanczos_groundstate, lanczos_sqw, lanczos_sqw_transverse,
                       lanczos_tridiag, rescaling_from_bounds, spectral_from_tridiagonal, symtridiag_eig,
-                      kpm_correlation_matrix, kpm_reconstruct_signed, kpm_site_moments, kpm_sqw_sites, site_project)
+                      kpm_correlation_matrix, kpm_reconstruct_signed, kpm_site_moments, kpm_sqw_sites, site_project,
+                      lanczos_eigenpairs, lowest_eigenpairs, spectral_gap, sym_eig)
 from .typicality import (chebyshev_imag_coeffs, current_expectation, dqt_sample, energy_current, energy_current_expectation,
                          energy_current_terms, spin_current, thermal_energy, thermal_state, typicality_correlation_function)
 from .observables import (bond_energies, bond_operator, connected_correlations, correlation_matrix, dimer_correlation_matrix,
                           dimer_structure_factor, magnetization_per_site, model_bonds, momentum_distribution,
                           static_structure_factor, structure_factor_Sq)
-from .symmetry import (is_symmetric, lowest_level, momentum_weights, permutation_compose, permutation_inverse, permute_sites,
+from .symmetry import (is_symmetric, lowest_level, lowest_levels, momentum_weights, permutation_compose, permutation_inverse, permute_sites,
                        quantum_numbers, reflect, spin_flip, subsystem_permutation, symmetric_operator, symmetry_apply,
                        symmetry_combine, symmetry_overlaps, symmetry_project, translate)
 from .operators import (Term, chirality_correlations, chirality_terms, hamiltonian_terms, multi_spin_expectation,

@@ -74,6 +74,11 @@ class sd_xop(C.Structure):
     _fields_ = [("batch", C.c_int), ("peer", C.c_int), ("kind", C.c_int), ("buf", C.c_int), ("offset", C.c_int64), ("count", C.c_int64)]
 
 
+class sd_eigs_info(C.Structure):
+    _fields_ = [("converged", C.c_int), ("restarts", C.c_int), ("applies", C.c_int64), ("basis_size", C.c_int),
+                ("workspace_vectors", C.c_int), ("next_level", C.c_double), ("have_next_level", C.c_int), ("scale", C.c_double)]
+
+
 class sd_comm_callbacks(C.Structure):
     _fields_ = [("user", C.c_void_p), ("exchange_start", EXCHANGE_START_FN), ("exchange_wait", EXCHANGE_WAIT_FN),
                 ("allreduce_sum", ALLREDUCE_FN)]
@@ -118,6 +123,11 @@ PROTOTYPES = {
     "sd_lanczos_extremal": (_i, [_vp, _vp, _i, _d, _vp, _u64, _i, _dp, _dp]),
     "sd_energy_bounds": (_i, [_vp, _vp, _i, _vp, _vp, _u64, _dp, _dp]),
     "sd_lanczos_groundstate": (_i, [_vp, _vp, _i, _d, _d, _dp, _u64, _dp, _dp, _ip]),
+    "sd_lanczos_eigenpairs": (_i, [_vp, _vp, _i, _i, _i, _d, _i64, _i, _vp, _u64, _dp, _vp, _dp, C.POINTER(sd_eigs_info)]),
+    "sd_lanczos_eigenpairs_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _i64, _i, _vp, _u64, _dp, _vp, _dp, C.POINTER(sd_eigs_info)]),
+    "sd_basis_rotate_dev": (_i, [_vp, _vp, _i64, _i64, _i, _dp, _i]),
+    "sd_block_dots_dev": (_i, [_vp, _i, _vp, _i64, _i, _vp, _i64, _dp]),
+    "sd_block_axpy_dev": (_i, [_vp, _i, _vp, _vp, _i64, _i, _dp, _i64]),
     "sd_lanczos_tridiag": (_i, [_vp, _vp, _vp, _i64, _i, _d, _dp, _dp, _ip, _dp]),
     "sd_krylov_evolve": (_i, [_vp, _vp, _i, _vp, _i64, _d, _i, _vp]),
     "sd_krylov_evolve_dev": (_i, [_vp, _vp, _i, _vp, _i64, _d, _i, _vp]),
@@ -205,6 +215,7 @@ PROTOTYPES = {
     "sd_nrm2sq_dev": (_i, [_vp, _i, _vp, _i64, _dp]),
     "sd_spin_operator": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp]),
     "sd_symtridiag_eig": (_i, [_i, _dp, _dp, _dp, _dp]),
+    "sd_sym_eig": (_i, [_i, _dp, _dp, _dp]),
     "sd_chebyshev_coeffs": (_i, [_i, _d, _d, _d, _dp]),
     "sd_fill_randn_dev": (_i, [_vp, _vp, _i64, _u64, _u64]),
     "sd_fill_randn_host": (_i, [_dp, _i64, _u64, _u64]),

@@ -2585,3 +2585,298 @@ extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, 
     std::memcpy(num + (size_t)2 * nA * k, h.data() + (size_t)mrow * k, sizeof(double) * 2 * (size_t)nA);
   return SD_OK;
 }); }
+
+// --------------------------------------------------------------------------
+// The lowest eigenpairs by thick-restart Lanczos (include/spindyn.h, sd_lanczos_eigenpairs)
+// --------------------------------------------------------------------------
+
+// eigen(Symmetric(A)) by cyclic Jacobi rotations (row-cyclic sweeps until the off-diagonal norm is below u |A|_F)
+extern "C" int sd_sym_eig(int n, const double *A_in, double *w, double *Z) {
+  if (n < 1 || n > SD_EIGS_MAX_BASIS || !A_in || !w || !Z) return SD_EARG;
+  try {
+    std::vector<double> A((size_t)n * n);
+    for (int c = 0; c < n; ++c)
+      for (int r = c; r < n; ++r) A[r + (size_t)n * c] = A[c + (size_t)n * r] = A_in[r + (size_t)n * c];
+    std::fill(Z, Z + (size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i) Z[i + (size_t)n * i] = 1.0;
+    double fro2 = 0.0;
+    for (double x : A) fro2 += x * x;
+    const double u = 1.1102230246251565e-16, stop2 = u * u * fro2;
+    bool done = n == 1 || fro2 == 0.0;
+    for (int sweep = 0; sweep < 100 && !done; ++sweep) {
+      for (int p = 0; p < n - 1; ++p)
+        for (int q = p + 1; q < n; ++q) {
+          const double apq = A[p + (size_t)n * q];
+          if (apq == 0.0) continue;
+          const double theta = (A[q + (size_t)n * q] - A[p + (size_t)n * p]) / (2.0 * apq);
+          const double t = std::copysign(1.0, theta) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+          const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+          double *cp = A.data() + (size_t)n * p, *cq = A.data() + (size_t)n * q;
+          for (int k = 0; k < n; ++k) { const double a = cp[k], b = cq[k]; cp[k] = c * a - s * b; cq[k] = s * a + c * b; }   // A <- A J
+          for (int k = 0; k < n; ++k) {                                                                               // A <- J^T A
+            double *col = A.data() + (size_t)n * k;
+            const double a = col[p], b = col[q];
+            col[p] = c * a - s * b; col[q] = s * a + c * b;
+          }
+          A[p + (size_t)n * q] = A[q + (size_t)n * p] = 0.0;
+          double *zp = Z + (size_t)n * p, *zq = Z + (size_t)n * q;
+          for (int k = 0; k < n; ++k) { const double a = zp[k], b = zq[k]; zp[k] = c * a - s * b; zq[k] = s * a + c * b; }
+        }
+      double off2 = 0.0;
+      for (int c = 0; c < n; ++c)
+        for (int r = c + 1; r < n; ++r) off2 += A[r + (size_t)n * c] * A[r + (size_t)n * c];
+      done = 2.0 * off2 <= stop2;
+    }
+    if (!done) return SD_EINTERNAL;
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return A[a + (size_t)n * a] < A[b + (size_t)n * b]; });
+    std::vector<double> zc(Z, Z + (size_t)n * n);
+    for (int k = 0; k < n; ++k) {
+      w[k] = A[order[k] + (size_t)n * order[k]];
+      std::memcpy(Z + (size_t)n * k, zc.data() + (size_t)n * order[k], sizeof(double) * n);
+    }
+    return SD_OK;
+  } catch (...) {
+    return SD_ENOMEM;
+  }
+}
+
+namespace {
+
+// include/spindyn.h, sd_lanczos_eigenpairs.  The basis is `mb` columns of ld doubles (ld even: the rotation then runs in its
+// 16-byte form) plus the work vector w; columns 0..c-1 are locked, c..c+l-1 hold the Ritz vectors kept by the last restart
+// (values th, couplings s to column c+l), column c+l onwards are the Lanczos vectors of the current block.
+int eigs_core(Op &op, int dtype, int nev, int basis_size, double tol, int64_t max_applies, int confirm, const void *psi0, bool on_dev,
+              uint64_t seed, double *evals, void *evecs, double *residuals, sd_eigs_info *info) {
+  sd_ctx *ctx = op.ctx;
+  const sd_model *m = op.m;
+  if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "lanczos_eigenpairs: a sharded model is not supported");
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (!evals || !residuals || !info) return sd_set_err(ctx, SD_EARG, "null output");
+  const int64_t N = m->N;
+  if (nev < 1) return sd_set_err(ctx, SD_EARG, "lanczos_eigenpairs: nev must be >= 1");
+  if (nev > SD_EIGS_MAX_NEV || nev > N) return sd_set_err(ctx, SD_EARG, "lanczos_eigenpairs: nev must be <= min(N, 24)");
+  if (basis_size > SD_EIGS_MAX_BASIS) return sd_set_err(ctx, SD_EARG, "lanczos_eigenpairs: basis_size must be <= 128");
+  if (basis_size < nev + 3 && basis_size < N) return sd_set_err(ctx, SD_EARG, "lanczos_eigenpairs: basis_size must be >= nev + 3 (or the basis dimension, if smaller)");
+  if (!(tol >= 0.0)) return sd_set_err(ctx, SD_EARG, "lanczos_eigenpairs: tol must be >= 0");
+  const int mb = (int)std::min<int64_t>(basis_size, N);
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  const int64_t nd = nc * N, ld = nd + (nd & 1);
+  const int64_t applies0 = ctx->n_applies;
+  *info = sd_eigs_info{};
+  info->basis_size = mb;
+  info->workspace_vectors = mb + 1;
+
+  DBuf V, w, sc, Qd;
+  RC(V.alloc(ctx, ld * mb)); RC(w.alloc(ctx, nd));
+  constexpr int CO = 2 * SD_EIGS_MAX_BASIS;                       // sc: coefficients of round 1 | of round 2 | |w|^2
+  RC(sc.alloc(ctx, 2 * CO + 2)); RC(Qd.alloc(ctx, (int64_t)SD_EIGS_MAX_BASIS * SD_EIGS_MAX_KEEP));
+  std::vector<double> hs(2 * CO + 2);
+  auto col = [&](int j) { return V.p + ld * (int64_t)j; };
+
+  // one round of classical Gram-Schmidt of w against columns 0..ncols-1 in blocks of 8: all dots first, then the subtractions
+  auto cgs_round = [&](int ncols, double *coef, double *n2) -> int {
+    for (int c0 = 0; c0 < ncols; c0 += SD_EIGS_BLOCK_COLS)
+      RC(sd_k_block_dots(ctx, nc, col(c0), ld, std::min(SD_EIGS_BLOCK_COLS, ncols - c0), w.p, N, coef + 2 * c0));
+    for (int c0 = 0; c0 < ncols; c0 += SD_EIGS_BLOCK_COLS)
+      RC(sd_k_block_axpy(ctx, nc, w.p, col(c0), ld, std::min(SD_EIGS_BLOCK_COLS, ncols - c0), coef + 2 * c0, N,
+                         c0 + SD_EIGS_BLOCK_COLS >= ncols ? n2 : nullptr));
+    return SD_OK;
+  };
+  int c = 0, l = 0, n_fresh = 0;
+  double scale = 0.0, scale_run = 0.0;
+  std::vector<double> lam, th, s;
+  // w (already filled) orthogonalised twice against the locked columns and normalised -> column c; *ok = 0: nothing was left of it
+  auto seat_start = [&](int *ok) -> int {
+    if (c > 0) { RC(cgs_round(c, sc.p, nullptr)); RC(cgs_round(c, sc.p + CO, nullptr)); }
+    int rc = 0;
+    const double nrm = norm_dev(op, w.p, nd, &rc); RC(rc);
+    *ok = nrm > 0.0 && std::isfinite(nrm);
+    if (*ok) RC(sd_k_scale_div(ctx, col(c), w.p, nd, nrm));
+    l = 0;
+    return SD_OK;
+  };
+  auto fresh_start = [&](int *ok) -> int {
+    RC(sd_k_fill_randn(ctx, w.p, nd, seed + 0x9E3779B97F4A7C15ULL * (uint64_t)(++n_fresh), 0));
+    return seat_start(ok);
+  };
+
+  // Thick-restart Lanczos on the columns behind the locked ones until `target` columns are locked.  *stopped: max_applies was
+  // reached; *exhausted: the locked columns span everything that is left.
+  auto run = [&](int target, bool *stopped, bool *exhausted) -> int {
+    *stopped = *exhausted = false;
+    while (c < target) {
+      const int mact = mb - c;
+      std::vector<double> T((size_t)mact * mact, 0.0);
+      for (int i = 0; i < l; ++i) { T[i + (size_t)mact * i] = th[i]; T[l + (size_t)mact * i] = T[i + (size_t)mact * l] = s[i]; }
+      int ja = l;
+      double beta = 0.0;
+      bool broke = false;
+      for (int j = c + l; j < mb; ++j) {
+        if (max_applies > 0 && ctx->n_applies - applies0 >= max_applies) { *stopped = true; return SD_OK; }
+        sd_epi_args ea;
+        RC(op.apply(dtype, w.p, col(j), SD_EPI_PLAIN, ea));
+        RC(cgs_round(j + 1, sc.p, nullptr)); RC(cgs_round(j + 1, sc.p + CO, sc.p + 2 * CO));
+        SD_HIP(ctx, hipMemcpyAsync(hs.data(), sc.p, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
+        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const int jj = j - c;
+        const double alpha = hs[2 * j] + hs[CO + 2 * j];
+        beta = std::sqrt(hs[2 * CO]);
+        T[jj + (size_t)mact * jj] = alpha;
+        ja = jj + 1;
+        scale_run = std::max(scale_run, std::fabs(alpha));
+        if (!(beta > 1e-12 * scale_run)) { broke = true; break; }
+        scale_run = std::max(scale_run, beta);
+        if (j + 1 < mb) {
+          T[jj + 1 + (size_t)mact * jj] = T[jj + (size_t)mact * (jj + 1)] = beta;
+          RC(sd_k_scale_div(ctx, col(j + 1), w.p, nd, beta));
+        }
+      }
+      std::vector<double> Tj((size_t)ja * ja), ev(ja), Z((size_t)ja * ja);
+      for (int a = 0; a < ja; ++a)
+        for (int b = 0; b < ja; ++b) Tj[b + (size_t)ja * a] = T[b + (size_t)mact * a];
+      if (sd_sym_eig(ja, Tj.data(), ev.data(), Z.data())) return sd_set_err(ctx, SD_EINTERNAL, "Jacobi eigen-solver did not converge");
+      scale = std::max(scale, std::max(std::fabs(ev[0]), std::fabs(ev[ja - 1])));
+      scale_run = std::max(scale_run, scale);
+      const double bl = broke ? 0.0 : beta;
+      const int need = target - c;
+      int nconv = 0;
+      while (nconv < ja && nconv < need && std::fabs(bl * Z[(ja - 1) + (size_t)ja * nconv]) <= tol * scale) ++nconv;
+      int kk = nconv;
+      if (!broke) {
+        const int buffer = std::min(8, std::max(2, (mact - need) / 3));
+        kk = std::max(nconv, std::min(std::min(need + buffer, SD_EIGS_MAX_KEEP), mact - 1));
+      }
+      if (kk > 0) {
+        SD_HIP(ctx, hipMemcpyAsync(Qd.p, Z.data(), sizeof(double) * (size_t)ja * kk, hipMemcpyHostToDevice, ctx->stream));
+        RC(sd_k_basis_rotate(ctx, col(c), ld, nd, ja, Qd.p, kk));
+        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ++info->restarts;
+      }
+      for (int i = 0; i < nconv; ++i) lam.push_back(ev[i]);
+      c += nconv;
+      if (broke) {
+        if (c >= target) { l = 0; return SD_OK; }
+        int ok = 0;
+        if (c < N && c < mb) RC(fresh_start(&ok));
+        if (!ok) { *exhausted = true; return SD_OK; }
+      } else {
+        l = kk - nconv;
+        th.assign(ev.begin() + nconv, ev.begin() + kk);
+        s.resize(l);
+        for (int i = 0; i < l; ++i) s[i] = bl * Z[(ja - 1) + (size_t)ja * (nconv + i)];
+        if (c + l >= mb) { *exhausted = c < target; return SD_OK; }      // no column left for the residual direction
+        RC(sd_k_scale_div(ctx, col(c + l), w.p, nd, beta));
+      }
+    }
+    return SD_OK;
+  };
+
+  // the start vector
+  int ok = 0;
+  if (psi0) RC(on_dev ? d2d(ctx, w.p, (const double *)psi0, nd) : h2d(ctx, w.p, psi0, nd));
+  else RC(sd_k_fill_randn(ctx, w.p, nd, seed, 0));
+  RC(seat_start(&ok));
+  if (!ok) return sd_set_err(ctx, SD_EZERO, "starting vector has zero norm");
+  bool stopped = false, exhausted = false;
+  RC(run(nev, &stopped, &exhausted));
+  // further copies of degenerate levels, levels the first sequence missed, and the first level above the window
+  while (confirm && !stopped && !exhausted && c >= nev && c < N && (mb - c >= 2 || mb == N) && c < mb) {
+    const int c0 = c;
+    RC(fresh_start(&ok));
+    if (!ok) break;
+    RC(run(c0 + 1, &stopped, &exhausted));
+    if (c == c0) break;
+    std::vector<double> sorted(lam.begin(), lam.begin() + c0);
+    std::sort(sorted.begin(), sorted.end());
+    const double mu = lam.back();
+    if (mu <= sorted[nev - 1] + tol * scale) continue;
+    info->next_level = mu; info->have_next_level = 1;
+    lam.pop_back(); c = c0;
+    break;
+  }
+
+  // ascending order, normalised, with the true residuals
+  std::vector<int> order(c);
+  for (int i = 0; i < c; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lam[a] < lam[b]; });
+  const int nout = std::min(nev, c);
+  if (c > nev) { info->next_level = lam[order[nev]]; info->have_next_level = 1; }   // a locked level beyond the window is the next one
+  for (int i = 0; i < nout; ++i) {
+    double *x = col(order[i]);
+    int rc = 0;
+    const double nrm = norm_dev(op, x, nd, &rc); RC(rc);
+    RC(sd_k_scale_div(ctx, x, x, nd, nrm));
+    sd_epi_args ea;
+    RC(op.apply(dtype, w.p, x, SD_EPI_PLAIN, ea));
+    RC(sd_k_sub2(ctx, w.p, x, nullptr, nd, lam[order[i]], 0.0));
+    residuals[i] = norm_dev(op, w.p, nd, &rc); RC(rc);
+    evals[i] = lam[order[i]];
+    if (evecs) {
+      double *dst = (double *)evecs + nd * (int64_t)i;
+      RC(on_dev ? d2d(ctx, dst, x, nd) : d2h(ctx, dst, x, nd));
+    }
+  }
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  info->converged = nout;
+  info->applies = ctx->n_applies - applies0;
+  info->scale = scale;
+  return SD_OK;
+}
+
+}  // namespace
+
+extern "C" int sd_lanczos_eigenpairs(sd_ctx *ctx, const sd_model *m, int dtype, int nev, int basis_size, double tol, int64_t max_applies,
+                                     int confirm, const void *psi0, uint64_t seed, double *evals, void *evecs, double *residuals,
+                                     sd_eigs_info *info) { return abi_guard(ctx, [&]() -> int {
+  Op op; RC(op.init(ctx, m, nullptr));
+  return eigs_core(op, dtype, nev, basis_size, tol, max_applies, confirm, psi0, false, seed, evals, evecs, residuals, info);
+}); }
+extern "C" int sd_lanczos_eigenpairs_dev(sd_ctx *ctx, const sd_model *m, int dtype, int nev, int basis_size, double tol,
+                                         int64_t max_applies, int confirm, const void *psi0, uint64_t seed, double *evals, void *evecs,
+                                         double *residuals, sd_eigs_info *info) { return abi_guard(ctx, [&]() -> int {
+  Op op; RC(op.init(ctx, m, nullptr));
+  return eigs_core(op, dtype, nev, basis_size, tol, max_applies, confirm, psi0, true, seed, evals, evecs, residuals, info);
+}); }
+
+// the solver's kernels on the caller's device vectors (include/spindyn.h)
+extern "C" int sd_basis_rotate_dev(sd_ctx *ctx, void *V, int64_t ld, int64_t n, int mm, const double *Q, int k) {
+  return abi_guard(ctx, [&]() -> int {
+  if (!ctx) return SD_EARG;
+  if (mm < 1 || k < 1 || k > mm || mm > SD_EIGS_MAX_BASIS || k > SD_EIGS_MAX_KEEP)
+    return sd_set_err(ctx, SD_EARG, "basis rotation: need 1 <= k <= m <= 128 and k <= 32");
+  if (!V || !Q || n < 0 || ld < n) return sd_set_err(ctx, SD_EARG, "bad argument");
+  SD_HIP(ctx, hipSetDevice(ctx->device));
+  DBuf Qd; RC(Qd.alloc(ctx, (int64_t)mm * k));
+  SD_HIP(ctx, hipMemcpyAsync(Qd.p, Q, sizeof(double) * (size_t)mm * k, hipMemcpyHostToDevice, ctx->stream));
+  RC(sd_k_basis_rotate(ctx, (double *)V, ld, n, mm, Qd.p, k));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}); }
+extern "C" int sd_block_dots_dev(sd_ctx *ctx, int dtype, const void *V, int64_t ld, int ncols, const void *w, int64_t n, double *out) {
+  return abi_guard(ctx, [&]() -> int {
+  if (!ctx) return SD_EARG;
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (ncols < 1 || ncols > SD_EIGS_BLOCK_COLS || !V || !w || !out || n < 0 || ld < n) return sd_set_err(ctx, SD_EARG, "bad argument");
+  SD_HIP(ctx, hipSetDevice(ctx->device));
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  DBuf o; RC(o.alloc(ctx, 2 * SD_EIGS_BLOCK_COLS));
+  RC(sd_k_block_dots(ctx, nc, (const double *)V, ld * nc, ncols, (const double *)w, n, o.p));
+  SD_HIP(ctx, hipMemcpyAsync(out, o.p, sizeof(double) * 2 * (size_t)ncols, hipMemcpyDeviceToHost, ctx->stream));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}); }
+extern "C" int sd_block_axpy_dev(sd_ctx *ctx, int dtype, void *w, const void *V, int64_t ld, int ncols, const double *coef, int64_t n) {
+  return abi_guard(ctx, [&]() -> int {
+  if (!ctx) return SD_EARG;
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (ncols < 1 || ncols > SD_EIGS_BLOCK_COLS || !V || !w || !coef || n < 0 || ld < n) return sd_set_err(ctx, SD_EARG, "bad argument");
+  SD_HIP(ctx, hipSetDevice(ctx->device));
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  DBuf cf; RC(cf.alloc(ctx, 2 * SD_EIGS_BLOCK_COLS));
+  SD_HIP(ctx, hipMemcpyAsync(cf.p, coef, sizeof(double) * 2 * (size_t)ncols, hipMemcpyHostToDevice, ctx->stream));
+  RC(sd_k_block_axpy(ctx, nc, (double *)w, (const double *)V, ld * nc, ncols, cf.p, n, nullptr));
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}); }

@@ -461,6 +461,17 @@ int sd_launch_cut_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *ps
 struct sd_site_perm;
 int sd_launch_site_permute(sd_ctx *ctx, const sd_model *m, int dtype, const sd_site_perm &pm, const void *x, void *out);
 
+// Kernels of the thick-restart eigen-solver (kernels_eigs.hip); queued on the context's stream, deterministic.
+#define SD_EIGS_MAX_BLOCKS 2048   // most blocks of one of their passes (256 threads each): where their grid-stride loops wrap
+#define SD_EIGS_BLOCK_COLS 8      // columns of one Gram-Schmidt block
+// V[r, c] <- sum_{j < m} V[r, j] Q[j, c], r < n (doubles), c < k, in place; Q_dev: m x k column-major on the device
+int sd_k_basis_rotate(sd_ctx *ctx, double *V, int64_t ld, int64_t n, int m, const double *Q_dev, int k);
+// out_dev[2c .. +1] = (re, im) of <V[:, c] | w>, c < ncols <= 8; N elements of nc doubles, ld in doubles
+int sd_k_block_dots(sd_ctx *ctx, int nc, const double *V, int64_t ld, int ncols, const double *w, int64_t N, double *out_dev);
+// w -= sum_c coef[c] V[:, c], coef_dev[2c .. +1] = (re, im); n2_dev != null: |w_new|^2 -> n2_dev[0]
+int sd_k_block_axpy(sd_ctx *ctx, int nc, double *w, const double *V, int64_t ld, int ncols, const double *coef_dev, int64_t N,
+                    double *n2_dev);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.

@@ -477,3 +477,89 @@ def symtridiag_eig(d, e, vectors=True):
     check(lib().sd_symtridiag_eig(n, d.ctypes.data_as(_dp), e.ctypes.data_as(_dp), w.ctypes.data_as(_dp),
                                   z.ctypes.data_as(_dp) if vectors else None))
     return (w, z) if vectors else w
+
+
+def sym_eig(A):
+    """eigen(Symmetric(A)) by cyclic Jacobi rotations (sd_sym_eig; n <= 128, the lower triangle is read) -> (w ascending, Z)."""
+    A = np.asfortranarray(A, dtype=np.float64)
+    n = A.shape[0]
+    if A.ndim != 2 or A.shape[1] != n:
+        raise DimensionMismatch("A must be square")
+    w, Z = np.empty(n), np.empty((n, n), order="F")
+    check(lib().sd_sym_eig(n, A.ctypes.data_as(_dp), w.ctypes.data_as(_dp), Z.ctypes.data_as(_dp)))
+    return w, Z
+
+
+@_with_operator
+def lanczos_eigenpairs(applyH, model, k=4, basis_size=None, tol=1e-10, max_applies=None, confirm=True, psi0=None, seed=0,
+                       vectors=True, dtype=None):
+    """The lowest k eigenpairs by thick-restart Lanczos in (basis_size + 1) device vectors (sd_lanczos_eigenpairs)
+    -> (E, X, info).  E: k ascending levels (info["converged"] of them when max_applies ended the run early); X: their states
+    in the columns of an (N, k) array -- a torch tensor on the model's device when psi0 is one, otherwise numpy; None with
+    vectors=False; info: converged, restarts, applies, basis_size, workspace_vectors, residuals, scale, next_level (the first level
+    above the returned ones, or None).  confirm=True looks for further copies of degenerate levels from fresh random vectors and
+    so returns every multiplicity; set it to False for an operator that projects onto a sector.  dtype: np.float64 or
+    np.complex128; default psi0's, else float64 for the built-in operator and complex128 for a callable."""
+    N = model.N
+    on_dev = _is_torch(psi0)
+    if dtype is None:
+        if psi0 is not None:
+            cplx = psi0.is_complex() if on_dev else np.iscomplexobj(psi0)
+        else:
+            cplx = applyH is not apply_H
+    else:
+        cplx = np.dtype(dtype) == np.complex128
+        if not cplx and np.dtype(dtype) != np.float64:
+            raise ArgumentError("dtype must be float64 or complex128")
+    code, npdt = (SD_C128, np.complex128) if cplx else (SD_F64, np.float64)
+    k = int(k)
+    if basis_size is None:
+        basis_size = min(N, max(2 * k + 8, 24))
+    E, res = np.zeros(max(k, 1)), np.zeros(max(k, 1))
+    info = _lib.sd_eigs_info()
+    args = (int(basis_size), float(tol), int(max_applies) if max_applies is not None else 200000, int(bool(confirm)))
+    if on_dev:
+        import torch
+        tdt = torch.complex128 if cplx else torch.float64
+        if len(psi0) != N:
+            raise DimensionMismatch(f"psi0 has length {len(psi0)}, expected {N}")
+        p0 = psi0.to(tdt).contiguous()
+        _bind_torch_stream(model, p0)
+        Xt = torch.empty((max(k, 1), N), dtype=tdt, device=p0.device) if vectors else None
+        check(lib().sd_lanczos_eigenpairs_dev(model.ctx.h, model.h, code, k, *args, p0.data_ptr(), int(seed), E.ctypes.data_as(_dp),
+                                              Xt.data_ptr() if vectors else None, res.ctypes.data_as(_dp), C.byref(info)),
+              model.ctx.h)
+        X = Xt[: info.converged].T if vectors else None
+    else:
+        p0 = None
+        if psi0 is not None:
+            p0 = np.ascontiguousarray(psi0, dtype=npdt)
+            if len(p0) != N:
+                raise DimensionMismatch(f"psi0 has length {len(p0)}, expected {N}")
+        Xn = np.zeros((N, max(k, 1)), dtype=npdt, order="F") if vectors else None
+        check(lib().sd_lanczos_eigenpairs(model.ctx.h, model.h, code, k, *args, _ptr(p0), int(seed), E.ctypes.data_as(_dp),
+                                          _ptr(Xn), res.ctypes.data_as(_dp), C.byref(info)), model.ctx.h)
+        X = Xn[:, : info.converged] if vectors else None
+    nc = info.converged
+    out = {"converged": nc, "restarts": info.restarts, "applies": int(info.applies), "basis_size": info.basis_size,
+           "workspace_vectors": info.workspace_vectors, "residuals": res[:nc].copy(), "scale": info.scale,
+           "next_level": info.next_level if info.have_next_level else None}
+    return E[:nc].copy(), X, out
+
+
+def lowest_eigenpairs(model, k=4, **kw):
+    """lanczos_eigenpairs with the built-in operator -> (E, X, info)."""
+    return lanczos_eigenpairs(apply_H, model, k=k, **kw)
+
+
+def spectral_gap(model, **kw):
+    """(E0, E1 - E0, degeneracy of E0) from the two lowest levels with confirmation.  degeneracy counts the levels within
+    tol * scale of E0 among the two returned levels and the next level, so it reads 1, 2 or 3 (3: at least threefold; ask
+    lowest_eigenpairs for more levels).  For a degenerate E0 the second value is 0 to rounding; the gap above the multiplet is
+    then next_level - E0 of lowest_eigenpairs(model, k=degeneracy)."""
+    kw.setdefault("vectors", False)
+    E, _, info = lowest_eigenpairs(model, k=min(2, model.N), confirm=True, **kw)
+    levels = list(E) + ([info["next_level"]] if info["next_level"] is not None else [])
+    eps = float(kw.get("tol", 1e-10)) * info["scale"]
+    deg = sum(1 for e in levels if e - levels[0] <= eps)
+    return float(E[0]), float(E[1] - E[0]) if len(E) > 1 else float("nan"), deg

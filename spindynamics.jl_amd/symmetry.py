@@ -373,3 +373,32 @@ def lowest_level(model, lanc_m=100, psi0=None, seed=0, tol=1e-12, **sector):
     if float(torch.linalg.vector_norm(p0)) == 0.0:
         raise ZeroNormError("the start vector has no component in the sector")
     return lanczos_extremal(op, model, lanc_m=lanc_m, tol=tol, psi0=p0.cpu().numpy(), seed=seed)[0]
+
+
+def lowest_levels(model, k, psi0=None, seed=0, **sector):
+    """The lowest k eigenpairs of H in a symmetry sector (momentum=, parity=, spin_flip=) -> (E, X): lanczos_eigenpairs of
+    symmetric_operator(model, **sector) in complex128, started from P psi0 (psi0 None: the seeded random complex vector); X is a
+    torch tensor (N, k) on the model's device.  basis_size=, tol= and max_applies= are passed on.  The call sets confirm=False: the
+    confirmation step starts from a fresh random vector, which would leave the sector (the solver sees P H P, whose levels outside
+    the sector are 0).  What it is for is done by the sector itself, which resolves the lattice degeneracies: the +-k partners of a
+    ring lie in different sectors.  k must not exceed the sector's dimension, for the same reason."""
+    import torch
+    from .solvers import lanczos_eigenpairs
+    kw = {n: sector.pop(n) for n in ("basis_size", "tol", "max_applies") if n in sector}
+    op = symmetric_operator(model, **sector)
+    dev = torch.device("cuda", model.ctx.device)
+    if psi0 is None:
+        x = torch.empty(model.N, dtype=torch.complex128, device=dev)
+        _bind_torch_stream(model, x)
+        check(lib().sd_fill_randn_dev(model.ctx.h, x.data_ptr(), 2 * model.N, int(seed), 0), model.ctx.h)
+    else:
+        if _is_torch(psi0) and psi0.device != dev:
+            raise ArgumentError("psi0 must be on the model's device")
+        x = torch.as_tensor(np.ascontiguousarray(psi0, dtype=np.complex128), device=dev) if not _is_torch(psi0) else psi0.to(torch.complex128)
+        if len(x) != model.N:
+            raise DimensionMismatch(f"psi0 has length {len(x)}, expected {model.N}")
+    p0 = symmetry_project(x, model, **sector)
+    if float(torch.linalg.vector_norm(p0)) == 0.0:
+        raise ZeroNormError("the start vector has no component in the sector")
+    E, X, _ = lanczos_eigenpairs(op, model, k=k, confirm=False, psi0=p0, seed=seed, **kw)
+    return E, X
