@@ -262,6 +262,54 @@ int sd_krylov_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0
  * has finished. */
 int sd_krylov_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n,
                          double dt, int kry_m, void *psit_out_c128_dev);
+/* ---- driven dynamics: H(t) = H0 + sum_k f_k(t) D_k with diagonal drives (not in the reference) ----
+ * H0 is the model as built.  A drive is D = sum_i site_w[i-1] S^z_i + sum_b zz_w[b] S^z_{zz_i[b]} S^z_{zz_j[b]}: site weights (L entries
+ * or NULL) plus a zz-bond list of its own (sites 1-based, as sd_model_create; a bond may repeat).  For coefficients c_k the library
+ * forms W_i = sum_k c_k site_w_k[i] (from 0.0, ascending k, one multiply then one add per term) and the concatenated bond list
+ * (drive order, then list order, weights c_k zz_w_k[b], not merged), and one elementwise kernel adds d(s) psi to H0 psi, where d(s) is
+ * the sequential sum, from 0.0, of the site terms +-W_i/2 in site order (skipped when no drive has site weights) and then the bond
+ * terms +-V_b/4 in list order (+ for parallel spins), each selected, not multiplied; then one multiply d * psi and one add per
+ * component.  Limits, answered with SD_EARG and a message: K <= SD_DRIVE_MAX, at most SD_DRIVE_MAX_BONDS bond terms in all, sites
+ * in 1..L, i != j, finite weights and coefficients, an unsharded model.
+ * sd_drive_check: the limits alone (host only).
+ * sd_diag_apply: out = (sum_k c_k D_k) psi, or that + y when y != NULL (y of psi's dtype; may be out).  out must not alias psi.
+ * sd_driven_apply: out = (H0 + sum_k c_k D_k) psi with the built-in H0 (operator level, as sd_apply: a caller's operator may call it,
+ *   which makes it an operator for every recursion that takes one).  out must not alias psi.
+ * sd_driven_evolve: for stage s = 0 .. n_stages-1, psi <- exp(-i tau[s] (H0 + sum_k coef[s K + k] D_k)) psi by the Krylov propagator
+ *   (krylov_time_evolve's arithmetic, normalised by every stage) with the state on the device between stages.  A stage whose
+ *   coefficients are all exactly zero (or K == 0) runs the built-in path of sd_krylov_evolve.  A caller's operator installed on the
+ *   context (sd_ctx_set_apply_callback) replaces H0 as in every recursion.  psi0 of `dtype`, psit ComplexF64
+ *   (psit may be a ComplexF64 psi0).  info (or NULL): stages run, operator applications, the smallest Lanczos beta seen.
+ * _dev: the vectors are device pointers; the calls return after the stream has finished. */
+#define SD_DRIVE_MAX 16
+#define SD_DRIVE_MAX_BONDS 128
+typedef struct sd_drive {
+  const double *site_w;     /* L entries or NULL */
+  int n_zz;
+  const int *zz_i;          /* n_zz entries each (NULL allowed when n_zz == 0) */
+  const int *zz_j;
+  const double *zz_w;
+} sd_drive;
+typedef struct sd_driven_info {
+  int stages;               /* stages run */
+  int64_t applies;          /* operator applications of the call */
+  double min_beta;          /* smallest Lanczos beta of all stages (+inf when no stage produced one) */
+} sd_driven_info;
+int sd_drive_check(const sd_model *m, const sd_drive *drives, int K);
+int sd_diag_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_drive *drives, int K,
+                  const double *coef, const void *y_host /* or NULL */, void *out_host);
+int sd_diag_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_drive *drives, int K,
+                      const double *coef, const void *y_dev /* or NULL */, void *out_dev);
+int sd_driven_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_drive *drives, int K,
+                    const double *coef, void *out_host);
+int sd_driven_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_drive *drives, int K,
+                        const double *coef, void *out_dev);
+int sd_driven_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, const sd_drive *drives, int K,
+                     int n_stages, const double *tau, const double *coef, int kry_m, void *psit_out_c128_host,
+                     sd_driven_info *info /* or NULL */);
+int sd_driven_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, const sd_drive *drives, int K,
+                         int n_stages, const double *tau, const double *coef, int kry_m, void *psit_out_c128_dev,
+                         sd_driven_info *info /* or NULL */);
 /* chebyshev_time_evolve   src/TimeEvolution/Chebyshev.jl:61-124  (psi0 ComplexF64) */
 int sd_chebyshev_evolve(sd_ctx *ctx, const sd_model *m, const void *psi0_c128_host, int64_t n, double dt,
                         int cheb_n, double Emin, double Emax, void *psit_out_c128_host);

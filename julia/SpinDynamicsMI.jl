@@ -22,6 +22,7 @@ export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_
        groundstate, lowest_eigenpairs, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
        chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, CutBlock, cut_blocks, cut_gram, permute_sites, site_permute_sources, subsystem_permutation, subsystem_gram, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
+       DiagonalDrive, field_drive, gradient_drive, zz_drive, drive_check, diagonal_apply, driven_apply, magnus_schedule, piecewise_schedule, stage_evolve, driven_time_evolve,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -996,6 +997,153 @@ function typicality_correlation_function(model::Model, β::Real, operator_i, ope
     wgt = [exp(2 * (s[4] - shift)) for s in samples]
     C = sum(wgt[k] .* samples[k][1] for k in 1:n_samples) ./ sum(wgt)
     return operator_i === :Sz_all ? C : vec(C)
+end
+
+# ---- driven dynamics: H(t) = H0 + Σ_k f_k(t) D_k with diagonal drives (include/spindyn.h, "driven dynamics"; DESIGN.md 24) ----
+# D = Σ_i site_weights[i] Sᶻ_i + Σ_b bond_weights[b] Sᶻ_i Sᶻ_j over bonds[b] = (i, j), sites 1-based; either part may be missing.
+struct DiagonalDrive
+    site_weights::Union{Nothing,Vector{Float64}}
+    zz_i::Vector{Cint}
+    zz_j::Vector{Cint}
+    bond_weights::Vector{Float64}
+end
+function DiagonalDrive(; site_weights=nothing, bonds=Tuple{Int,Int}[], bond_weights=nothing)
+    w = bond_weights === nothing ? ones(Float64, length(bonds)) : Vector{Float64}(bond_weights)
+    length(w) == length(bonds) || throw(ArgumentError("bond_weights must have one entry per bond"))
+    return DiagonalDrive(site_weights === nothing ? nothing : Vector{Float64}(site_weights), Cint[b[1] for b in bonds],
+                         Cint[b[2] for b in bonds], w)
+end
+field_drive(model::Model; weights=nothing) = DiagonalDrive(site_weights=weights === nothing ? ones(model.L) : weights)
+gradient_drive(model::Model) = DiagonalDrive(site_weights=collect(1:model.L) .- (model.L + 1) / 2)
+zz_drive(model::Model; bonds=nothing, weights=nothing) =
+    DiagonalDrive(bonds=bonds === nothing ? [(b[1], b[2]) for b in model.zz_list] : bonds, bond_weights=weights)
+
+struct CDrive                # sd_drive
+    site_w::Ptr{Float64}
+    n_zz::Cint
+    zz_i::Ptr{Cint}
+    zz_j::Ptr{Cint}
+    zz_w::Ptr{Float64}
+end
+mutable struct DrivenInfo    # sd_driven_info
+    stages::Cint
+    applies::Int64
+    min_beta::Float64
+    DrivenInfo() = new(0, 0, Inf)
+end
+# the sd_drive array of a list; the pointers are into the drives' own arrays: keep `drives` alive (GC.@preserve) while it is in use
+function pack_drives(model::Model, drives::Vector{DiagonalDrive})
+    for d in drives
+        d.site_weights === nothing || length(d.site_weights) == model.L || throw(ArgumentError("site_weights needs L entries"))
+    end
+    return CDrive[CDrive(d.site_weights === nothing ? Ptr{Float64}(C_NULL) : pointer(d.site_weights), length(d.zz_i), pointer(d.zz_i),
+                         pointer(d.zz_j), pointer(d.bond_weights)) for d in drives]
+end
+
+function drive_check(model::Model, drives::Vector{DiagonalDrive})
+    GC.@preserve drives begin
+        arr = pack_drives(model, drives)
+        check(ccall((:sd_drive_check, libspindyn), Cint, (Ptr{Cvoid}, Ptr{CDrive}, Cint), model.h, arr, length(arr)), model.ctx.h)
+    end
+    return nothing
+end
+
+# (Σ_k coefs[k] D_k) ψ, plus y when given
+function diagonal_apply(ψ::Vector{T}, model::Model, drives::Vector{DiagonalDrive}, coefs::AbstractVector;
+                        y::Union{Nothing,Vector{T}}=nothing) where {T<:Union{Float64,ComplexF64}}
+    out = similar(ψ)
+    c = Vector{Float64}(coefs)
+    GC.@preserve drives begin
+        arr = pack_drives(model, drives)
+        check(ccall((:sd_diag_apply, libspindyn), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{CDrive}, Cint, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+                    model.ctx.h, model.h, dtype_code(T), ψ, length(ψ), arr, length(arr), c, y === nothing ? C_NULL : y, out), model.ctx.h)
+    end
+    return out
+end
+
+# out = (H0 + Σ_k coefs[k] D_k) ψ
+function driven_apply(out::Vector{T}, ψ::Vector{T}, model::Model, drives::Vector{DiagonalDrive},
+                      coefs::AbstractVector) where {T<:Union{Float64,ComplexF64}}
+    c = Vector{Float64}(coefs)
+    GC.@preserve drives begin
+        arr = pack_drives(model, drives)
+        check(ccall((:sd_driven_apply, libspindyn), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{CDrive}, Cint, Ptr{Float64}, Ptr{Cvoid}),
+                    model.ctx.h, model.h, dtype_code(T), ψ, length(ψ), arr, length(arr), c, out), model.ctx.h)
+    end
+    return out
+end
+
+# (tau, coef): order 2 the midpoint rule; order 4 the commutator-free Magnus scheme of Alvermann and Fehske, two stages of dt/2 per
+# step, the earlier one with c = 2 (α₂ f(t₁) + α₁ f(t₂)), the later one with c = 2 (α₁ f(t₁) + α₂ f(t₂)).  coef is K x stages
+# (column-major: stage s holds coef[:, s], which is the layout sd_driven_evolve reads).
+function magnus_schedule(functions::Vector, t0::Real, dt::Real, n_steps::Int; order::Int=4)
+    order in (2, 4) || throw(ArgumentError("order must be 2 or 4"))
+    K = length(functions)
+    per = order == 2 ? 1 : 2
+    tau = fill(Float64(dt) / per, per * n_steps)
+    coef = zeros(Float64, K, per * n_steps)
+    a1, a2 = (3 - 2 * sqrt(3)) / 12, (3 + 2 * sqrt(3)) / 12
+    for s in 0:n_steps-1
+        t = t0 + s * dt
+        if order == 2
+            coef[:, s+1] = [Float64(f(t + dt / 2)) for f in functions]
+        else
+            f1 = [Float64(f(t + (1 / 2 - sqrt(3) / 6) * dt)) for f in functions]
+            f2 = [Float64(f(t + (1 / 2 + sqrt(3) / 6) * dt)) for f in functions]
+            coef[:, 2s+1] = 2 .* (a2 .* f1 .+ a1 .* f2)
+            coef[:, 2s+2] = 2 .* (a1 .* f1 .+ a2 .* f2)
+        end
+    end
+    return tau, coef
+end
+
+# segments = [(duration, [c_1, ..., c_K]), ...]: a protocol that is constant on intervals
+function piecewise_schedule(segments::Vector)
+    tau = Float64[s[1] for s in segments]
+    coef = zeros(Float64, length(segments[1][2]), length(segments))
+    for (k, s) in enumerate(segments)
+        coef[:, k] = s[2]
+    end
+    return tau, coef
+end
+
+# ψ <- exp(-i tau[s] (H0 + Σ_k coef[k, s] D_k)) ψ for every stage in one call -> (ψ, info)
+function stage_evolve(model::Model, ψ0::AbstractVector, drives::Vector{DiagonalDrive}, tau::Vector{Float64}, coef::Matrix{Float64};
+                      kry_m::Int=30)
+    x = eltype(ψ0) <: Complex ? Vector{ComplexF64}(ψ0) : Vector{Float64}(ψ0)
+    size(coef) == (length(drives), length(tau)) || throw(ArgumentError("coef must be K x stages"))
+    out = Vector{ComplexF64}(undef, length(x))
+    info = DrivenInfo()
+    GC.@preserve drives begin
+        arr = pack_drives(model, drives)
+        check(ccall((:sd_driven_evolve, libspindyn), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{CDrive}, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cvoid},
+                     Ref{DrivenInfo}),
+                    model.ctx.h, model.h, dtype_code(eltype(x)), x, length(x), arr, length(arr), length(tau), tau, coef, kry_m, out,
+                    info), model.ctx.h)
+    end
+    return out, (stages=Int(info.stages), applies=info.applies, min_beta=info.min_beta)
+end
+
+# ψ(t0 + n_steps dt) under H(t) = H0 + Σ_k functions[k](t) D_k; measure(t, ψ) is called at t0 and after every measure_every steps
+function driven_time_evolve(model::Model, ψ0::AbstractVector, drives::Vector{DiagonalDrive}, functions::Vector, t0::Real, dt::Real,
+                            n_steps::Int; order::Int=4, kry_m::Int=30, measure=nothing, measure_every::Int=1)
+    tau, coef = magnus_schedule(functions, t0, dt, n_steps; order=order)
+    per = length(tau) ÷ n_steps
+    ψ = ψ0
+    results = Any[]
+    measure === nothing || push!(results, measure(Float64(t0), ψ))
+    done = 0
+    while done < n_steps
+        k = measure === nothing ? n_steps : min(measure_every, n_steps - done)
+        rng = per*done+1:per*(done+k)
+        ψ, _ = stage_evolve(model, ψ, drives, tau[rng], coef[:, rng]; kry_m=kry_m)
+        done += k
+        measure === nothing || push!(results, measure(t0 + done * dt, ψ))
+    end
+    return ψ, results
 end
 
 end # module

@@ -79,6 +79,16 @@ class sd_eigs_info(C.Structure):
                 ("workspace_vectors", C.c_int), ("next_level", C.c_double), ("have_next_level", C.c_int), ("scale", C.c_double)]
 
 
+class sd_drive(C.Structure):
+    """one diagonal drive (include/spindyn.h): site weights (L doubles or NULL) and a zz-bond list of its own, sites 1-based"""
+    _fields_ = [("site_w", C.POINTER(C.c_double)), ("n_zz", C.c_int), ("zz_i", C.POINTER(C.c_int)), ("zz_j", C.POINTER(C.c_int)),
+                ("zz_w", C.POINTER(C.c_double))]
+
+
+class sd_driven_info(C.Structure):
+    _fields_ = [("stages", C.c_int), ("applies", C.c_int64), ("min_beta", C.c_double)]
+
+
 class sd_comm_callbacks(C.Structure):
     _fields_ = [("user", C.c_void_p), ("exchange_start", EXCHANGE_START_FN), ("exchange_wait", EXCHANGE_WAIT_FN),
                 ("allreduce_sum", ALLREDUCE_FN)]
@@ -131,6 +141,13 @@ PROTOTYPES = {
     "sd_lanczos_tridiag": (_i, [_vp, _vp, _vp, _i64, _i, _d, _dp, _dp, _ip, _dp]),
     "sd_krylov_evolve": (_i, [_vp, _vp, _i, _vp, _i64, _d, _i, _vp]),
     "sd_krylov_evolve_dev": (_i, [_vp, _vp, _i, _vp, _i64, _d, _i, _vp]),
+    "sd_drive_check": (_i, [_vp, C.POINTER(sd_drive), _i]),
+    "sd_diag_apply": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, _dp, _vp, _vp]),
+    "sd_diag_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, _dp, _vp, _vp]),
+    "sd_driven_apply": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, _dp, _vp]),
+    "sd_driven_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, _dp, _vp]),
+    "sd_driven_evolve": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, _i, _dp, _dp, _i, _vp, C.POINTER(sd_driven_info)]),
+    "sd_driven_evolve_dev": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, _i, _dp, _dp, _i, _vp, C.POINTER(sd_driven_info)]),
     "sd_chebyshev_evolve": (_i, [_vp, _vp, _vp, _i64, _d, _i, _d, _d, _vp]),
     "sd_chebyshev_evolve_dev": (_i, [_vp, _vp, _vp, _i64, _d, _i, _d, _d, _vp]),
     "sd_kpm_moments": (_i, [_vp, _vp, _vp, _i64, _i, _d, _d, _dp]),

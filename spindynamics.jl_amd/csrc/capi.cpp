@@ -1099,3 +1099,65 @@ int sd_subsystem_gram_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void 
 }
 
 }  // extern "C"
+
+// ---- diagonal drives: the limits of a drive list and the table of one stage's effective operator ----
+// coef == null: the limits alone, nothing is written to `out`.
+int sd_drive_build(const sd_model *m, const sd_drive *drives, int K, const double *coef, sd_drive_table &out, std::string &err) {
+  if (!m) { err = "null model"; return SD_EARG; }
+  if (K < 0 || K > SD_DRIVE_MAX) { err = "the number of drives must be 0.." + std::to_string(SD_DRIVE_MAX); return SD_EARG; }
+  if (K > 0 && !drives) { err = "null drive list"; return SD_EARG; }
+  if (m->L < 1 || m->L > SD_MAX_L) { err = "diagonal drives need 1 <= L <= 63"; return SD_EARG; }
+  if (m->nranks != 1) { err = "diagonal drives need an unsharded model"; return SD_EARG; }
+  const int L = m->L;
+  int nb = 0;
+  bool sites = false;
+  for (int k = 0; k < K; ++k) {
+    const sd_drive &d = drives[k];
+    if (coef && !std::isfinite(coef[k])) { err = "drive coefficient " + std::to_string(k) + " is not finite"; return SD_EARG; }
+    if (d.site_w) {
+      sites = true;
+      for (int i = 0; i < L; ++i)
+        if (!std::isfinite(d.site_w[i])) { err = "drive " + std::to_string(k) + ": a site weight is not finite"; return SD_EARG; }
+    }
+    if (d.n_zz < 0) { err = "drive " + std::to_string(k) + ": negative bond count"; return SD_EARG; }
+    if (d.n_zz > 0 && (!d.zz_i || !d.zz_j || !d.zz_w)) { err = "drive " + std::to_string(k) + ": null bond list"; return SD_EARG; }
+    if (d.n_zz > SD_DRIVE_MAX_BONDS - nb) {
+      err = "more than " + std::to_string(SD_DRIVE_MAX_BONDS) + " zz terms in the drives together";
+      return SD_EARG;
+    }
+    for (int b = 0; b < d.n_zz; ++b) {
+      const int i = d.zz_i[b], j = d.zz_j[b];
+      if (i < 1 || i > L || j < 1 || j > L) { err = "drive " + std::to_string(k) + ": a bond site is outside 1..L"; return SD_EARG; }
+      if (i == j) { err = "drive " + std::to_string(k) + ": the two sites of a bond must differ"; return SD_EARG; }
+      if (!std::isfinite(d.zz_w[b])) { err = "drive " + std::to_string(k) + ": a bond weight is not finite"; return SD_EARG; }
+    }
+    nb += d.n_zz;
+  }
+  if (!coef) return SD_OK;
+  std::memset(&out, 0, sizeof(out));
+  out.has_sites = sites ? 1 : 0;
+  out.n_bonds = nb;
+  for (int i = 0; i < L; ++i) {
+    double W = 0.0;
+    for (int k = 0; k < K; ++k)
+      if (drives[k].site_w) { const double t = coef[k] * drives[k].site_w[i]; W = W + t; }
+    out.wh[i] = W * 0.5;
+  }
+  int at = 0;
+  for (int k = 0; k < K; ++k)
+    for (int b = 0; b < drives[k].n_zz; ++b, ++at) {
+      out.vq[at] = (coef[k] * drives[k].zz_w[b]) * 0.25;
+      out.bits[at] = (uint32_t)((drives[k].zz_i[b] - 1) | ((drives[k].zz_j[b] - 1) << 8));
+    }
+  return SD_OK;
+}
+
+extern "C" int sd_drive_check(const sd_model *m, const sd_drive *drives, int K) {
+  if (!m) return SD_EARG;
+  return cut_guard(m->ctx, [&]() -> int {
+    std::string err;
+    sd_drive_table none;
+    const int rc = sd_drive_build(m, drives, K, nullptr, none, err);
+    return rc ? sd_set_err(m->ctx, rc, "sd_drive_check: " + err) : SD_OK;
+  });
+}

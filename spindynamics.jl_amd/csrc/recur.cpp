@@ -98,6 +98,7 @@ struct Op {
   bool overlap = true;       // interior tiles run while the exchange is in flight
   bool use_callback = true;  // false: always the built-in operator (the operator-level entry sd_apply_sharded, which a caller's
                              // operator may itself call on a sharded model: include/spindyn.h, sd_ctx_set_apply_callback)
+  const sd_drive_table *drive = nullptr;   // a diagonal drive on top of the operator (driven_evolve_core), or null
 
   int init(sd_ctx *c, const sd_model *mm, sd_comm *cm) {
     if (!c) return SD_EARG;
@@ -116,6 +117,7 @@ struct Op {
   // out = epilogue(H psi) on the owned rows.  Sharded: pack (cell mode), post the exchange, interior tiles, wait, boundary tiles.
   int apply(int dtype, double *out, const double *psi, int epi, sd_epi_args ea) {
     ++ctx->n_applies;
+    if (drive) return apply_driven(dtype, out, psi, epi, ea);
     if (use_callback && ctx->user_apply) return user_op(ctx, dtype, out, psi, n, epi, ea);
     if (m->nranks == 1) return sd_launch_apply(ctx, m, dtype, out, psi, epi, ea, 0);
     ea.halo = halo.p;
@@ -129,6 +131,18 @@ struct Op {
     }
     RC(sd_comm_exchange_wait(ctx, comm, m));
     return sd_launch_apply(ctx, m, dtype, out, psi, epi, ea, 0);
+  }
+  // out = epilogue((H0 + D) psi): H0 psi into out by the caller's operator or the built-in apply, then the drive pass with the
+  // recursion's epilogue over out in place (kernels_drive.hip).  Unsharded models.
+  int apply_driven(int dtype, double *out, const double *psi, int epi, const sd_epi_args &ea) {
+    if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "diagonal drives need an unsharded model");
+    if (use_callback && ctx->user_apply) {
+      if (ctx->user_apply(ctx->user_apply_data, dtype, out, psi, n, (void *)ctx->stream))
+        return sd_set_err(ctx, SD_ECOMM, "the apply callback returned an error");
+    } else {
+      RC(sd_launch_apply(ctx, m, dtype, out, psi, SD_EPI_PLAIN, sd_epi_args(), 0));
+    }
+    return sd_launch_drive_epilogue(ctx, m, dtype, out, out, psi, epi, ea, *drive);
   }
   // device scalars <- their sum over the ranks (in place, ordered on the context's stream)
   int reduce(double *dev, int count) { return sd_comm_allreduce_dev(ctx, comm, dev, count); }
@@ -167,11 +181,11 @@ int peek_breakdown(sd_ctx *ctx, const double *d_be, int count, double tol, std::
 // built-in operator on an unsharded tiled plan of at most 16384 tiles, vectors of at most 2^22 rows (launch-bound sizes).
 bool launches_shareable(const Op &op) {
   const sd_model *m = op.m;
-  return op.ctx->q_batch && m->nranks == 1 && !op.ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 16384 && op.n <= ((int64_t)1 << 22);
+  return op.ctx->q_batch && m->nranks == 1 && !op.ctx->user_apply && !op.drive && m->p >= 0 && m->dm.n_singles <= 16384 && op.n <= ((int64_t)1 << 22);
 }
 bool lanczos_fused_ok(const Op &op, int Qb) {
   const sd_model *m = op.m;
-  return m->nranks == 1 && !op.ctx->user_apply && m->p >= 0 && m->dm.n_singles <= 4096 && op.n <= ((int64_t)1 << 22) &&
+  return m->nranks == 1 && !op.ctx->user_apply && !op.drive && m->p >= 0 && m->dm.n_singles <= 4096 && op.n <= ((int64_t)1 << 22) &&
          (int64_t)Qb * op.n * 16 * 3 <= ((int64_t)4 << 30);
 }
 int lanczos_fused(Op &op, int Qb, double *u0, int mm, int form, int negate, double tol, std::vector<double> &alpha,
@@ -852,7 +866,7 @@ extern "C" int sd_lanczos_tridiag(sd_ctx *ctx, const sd_model *m, const void *v,
 // projection; psit = exp(-dt H) psi0 / |.| and *log_norm = ln |exp(-dt H) psi0| (the reference returns the un-normalised vector;
 // the weights are formed as exp(-dt (theta_l - theta_min)) and dt theta_min goes into the logarithm, so nothing overflows).
 static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, double dt, int kry_m, void *psit, bool on_dev,
-                              double *log_norm = nullptr) {
+                              double *log_norm = nullptr, double *min_beta = nullptr) {
   sd_ctx *ctx = op.ctx;
   if (!psi0 || !psit) return sd_set_err(ctx, SD_EARG, "null vector");
   auto emit = [&](const double *src) -> int {          // result to the caller
@@ -930,6 +944,7 @@ static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, do
     alr[j - 1] = hostab[2 * (size_t)(j - 1)];
     if (j < kry_m) {
       beta[j - 1] = hostab[2 * (size_t)kry_m + (j - 1)];
+      if (min_beta && !(std::fabs(beta[j - 1]) >= *min_beta)) *min_beta = std::fabs(beta[j - 1]);   // driven_evolve_core's record
       if (!(std::fabs(beta[j - 1]) >= 1e-14)) { m_eff = j; break; }                       // :162-168
     }
   }
@@ -2879,4 +2894,120 @@ extern "C" int sd_block_axpy_dev(sd_ctx *ctx, int dtype, void *w, const void *V,
   RC(sd_k_block_axpy(ctx, nc, (double *)w, (const double *)V, ld * nc, ncols, cf.p, n, nullptr));
   SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SD_OK;
+}); }
+
+// ---- driven dynamics: H(t) = H0 + sum_k f_k(t) D_k with diagonal drives ----
+namespace {
+
+int drive_table(sd_ctx *ctx, const sd_model *m, const sd_drive *drives, int K, const double *coef, sd_drive_table &tb) {
+  std::string err;
+  const int rc = sd_drive_build(m, drives, K, coef, tb, err);
+  return rc ? sd_set_err(ctx, rc, err) : SD_OK;
+}
+
+// out = (sum_k coef[k] D_k) psi (+ y), or with_h0: out = (H0 + sum_k coef[k] D_k) psi with the built-in H0 (operator level, as
+// sd_apply: a caller's operator may call it)
+int drive_apply_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const sd_drive *drives, int K,
+                     const double *coef, const void *y, void *out, bool with_h0, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  if (K > 0 && !coef) return sd_set_err(ctx, SD_EARG, "null coefficients");
+  const double none = 0.0;
+  sd_drive_table tb;
+  RC(drive_table(ctx, m, drives, K, coef ? coef : &none, tb));
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!psi || !out) return sd_set_err(ctx, SD_EARG, "null argument");
+  if (on_dev && out == psi) return sd_set_err(ctx, SD_EARG, "out must not alias psi");
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  DBuf in, res;
+  const double *p = (const double *)psi, *yd = (const double *)y;
+  double *o = (double *)out;
+  if (!on_dev) {
+    RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi, nc * n)); p = in.p;
+    RC(res.alloc(ctx, nc * n)); o = res.p;
+    if (y) { RC(h2d(ctx, res.p, y, nc * n)); yd = res.p; }
+  }
+  if (with_h0) {
+    op.use_callback = false;
+    op.drive = &tb;
+    RC(op.apply(dtype, o, p, SD_EPI_PLAIN, sd_epi_args()));
+  } else {
+    RC(sd_launch_drive_epilogue(ctx, m, dtype, o, yd, p, SD_EPI_PLAIN, sd_epi_args(), tb));
+  }
+  if (!on_dev) return d2h(ctx, out, o, nc * n);
+  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SD_OK;
+}
+
+// psi <- exp(-i tau_s (H0 + sum_k coef[s K + k] D_k)) psi for s = 0 .. n_stages-1 by krylov_evolve_core on the driven operator, the
+// state on the device between stages.  The work vectors of a stage go back to the context's pool and the next stage takes the same
+// blocks: they are allocated once.  A stage without a table (K == 0, or every coefficient exactly zero) runs the built-in path.
+int driven_evolve_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const sd_drive *drives, int K,
+                       int n_stages, const double *tau, const double *coef, int kry_m, void *psit, bool on_dev, sd_driven_info *info) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (info) { info->stages = 0; info->applies = 0; info->min_beta = INFINITY; }
+  if (!psi0 || !psit) return sd_set_err(ctx, SD_EARG, "null vector");
+  if (n_stages < 1 || !tau) return sd_set_err(ctx, SD_EARG, "a driven evolution needs at least one stage and its durations");
+  if (K > 0 && !coef) return sd_set_err(ctx, SD_EARG, "null coefficients");
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (n != op.n) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (kry_m < 1) return sd_set_err(ctx, SD_EARG, "kry_m must be >= 1");
+  sd_drive_table tb;
+  RC(drive_table(ctx, m, drives, K, nullptr, tb));                       // the limits, before anything runs
+  for (int s = 0; s < n_stages; ++s) {
+    if (!std::isfinite(tau[s])) return sd_set_err(ctx, SD_EARG, "a stage duration is not finite");
+    for (int k = 0; k < K; ++k)
+      if (!std::isfinite(coef[(size_t)s * K + k])) return sd_set_err(ctx, SD_EARG, "a stage coefficient is not finite");
+  }
+  const int nc = dtype == SD_C128 ? 2 : 1;
+  DBuf in, state;
+  const double *src = (const double *)psi0;
+  double *cur = (double *)psit;
+  if (!on_dev) {
+    RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi0, nc * n)); src = in.p;
+    RC(state.alloc(ctx, 2 * n)); cur = state.p;
+  }
+  const int64_t applies0 = ctx->n_applies;
+  double min_beta = INFINITY;
+  for (int s = 0; s < n_stages; ++s) {
+    const double *c = K > 0 ? coef + (size_t)s * K : nullptr;
+    bool driven = false;
+    for (int k = 0; k < K; ++k) driven = driven || c[k] != 0.0;
+    op.drive = nullptr;
+    if (driven) { RC(drive_table(ctx, m, drives, K, c, tb)); op.drive = &tb; }
+    RC(krylov_evolve_core(op, s == 0 ? dtype : SD_C128, s == 0 ? src : cur, n, tau[s], kry_m, cur, true, nullptr, &min_beta));
+    if (info) { info->stages = s + 1; info->applies = ctx->n_applies - applies0; info->min_beta = min_beta; }
+  }
+  op.drive = nullptr;
+  if (!on_dev) return d2h(ctx, psit, cur, 2 * n);
+  return SD_OK;
+}
+
+}  // namespace
+
+extern "C" int sd_diag_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_drive *drives, int K,
+                             const double *coef, const void *y_host, void *out_host) { return abi_guard(ctx, [&]() -> int {
+  return drive_apply_core(ctx, m, dtype, psi_host, n, drives, K, coef, y_host, out_host, false, false);
+}); }
+extern "C" int sd_diag_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_drive *drives, int K,
+                                 const double *coef, const void *y_dev, void *out_dev) { return abi_guard(ctx, [&]() -> int {
+  return drive_apply_core(ctx, m, dtype, psi_dev, n, drives, K, coef, y_dev, out_dev, false, true);
+}); }
+extern "C" int sd_driven_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_drive *drives, int K,
+                               const double *coef, void *out_host) { return abi_guard(ctx, [&]() -> int {
+  return drive_apply_core(ctx, m, dtype, psi_host, n, drives, K, coef, nullptr, out_host, true, false);
+}); }
+extern "C" int sd_driven_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_drive *drives,
+                                   int K, const double *coef, void *out_dev) { return abi_guard(ctx, [&]() -> int {
+  return drive_apply_core(ctx, m, dtype, psi_dev, n, drives, K, coef, nullptr, out_dev, true, true);
+}); }
+extern "C" int sd_driven_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, const sd_drive *drives, int K,
+                                int n_stages, const double *tau, const double *coef, int kry_m, void *psit_host,
+                                sd_driven_info *info) { return abi_guard(ctx, [&]() -> int {
+  return driven_evolve_core(ctx, m, dtype, psi0_host, n, drives, K, n_stages, tau, coef, kry_m, psit_host, false, info);
+}); }
+extern "C" int sd_driven_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, const sd_drive *drives,
+                                    int K, int n_stages, const double *tau, const double *coef, int kry_m, void *psit_dev,
+                                    sd_driven_info *info) { return abi_guard(ctx, [&]() -> int {
+  return driven_evolve_core(ctx, m, dtype, psi0_dev, n, drives, K, n_stages, tau, coef, kry_m, psit_dev, true, info);
 }); }

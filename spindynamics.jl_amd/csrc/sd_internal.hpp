@@ -472,6 +472,26 @@ int sd_k_block_dots(sd_ctx *ctx, int nc, const double *V, int64_t ld, int ncols,
 int sd_k_block_axpy(sd_ctx *ctx, int nc, double *w, const double *V, int64_t ld, int ncols, const double *coef_dev, int64_t N,
                     double *n2_dev);
 
+// Diagonal drives (kernels_drive.hip): D = sum_i W_i S^z_i + sum_b V_b S^z_{i_b} S^z_{j_b}, the effective operator of one
+// stage of a driven evolution.  The table is uniform data handed to the kernel by value (2 KiB of kernel arguments): the halves
+// W_i / 2 and the quarters V_b / 4 are the exact magnitudes of the terms, which the kernel selects and adds in this order.
+// SD_DRIVE_MAX drives of one call, SD_DRIVE_MAX_BONDS zz terms of all drives together (include/spindyn.h).
+struct sd_drive_table {
+  int has_sites;                          // 0: no drive has site weights, the site loop is skipped
+  int n_bonds;
+  double wh[SD_MAX_L + 1];                // W_i / 2, i < L
+  double vq[SD_DRIVE_MAX_BONDS];          // V_b / 4 in list order
+  uint32_t bits[SD_DRIVE_MAX_BONDS];      // bi | bj << 8, 0-based bits of the bond's sites (32-bit words: scalar loads)
+};
+// The table of sum_k coef[k] D_k (capi.cpp; host only): W_i = sum_k coef[k] * w_{k,i} from 0.0 in ascending k, one multiply and one
+// add per term; bond weights coef[k] * v_{k,b}, drive order then list order.  SD_EARG with a message in `err`: see sd_drive_check.
+int sd_drive_build(const sd_model *m, const sd_drive *drives, int K, const double *coef, sd_drive_table &out, std::string &err);
+// out[r] = epilogue(h[r] + d(s_r) psi[r]) on the rows of an unsharded model with device tables: the step of a recursion on
+// H0 + D given h = H0 psi.  out may alias h; psi must not alias out.  The sums of a DOT / KPM / RESCALE_DOT epilogue are reduced as
+// sd_launch_epilogue_only reduces them.  h == null: h = 0.  Queued on the context's stream, deterministic.
+int sd_launch_drive_epilogue(sd_ctx *ctx, const sd_model *m, int dtype, void *out, const void *h, const void *psi, int epi,
+                             const sd_epi_args &ea, const sd_drive_table &table);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.
