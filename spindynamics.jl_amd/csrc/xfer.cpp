@@ -10,80 +10,14 @@
 //   SD_XFER_CHUNK_MB (default 32)                             SD_XFER_MIN_MB (default 16: below it, plain)
 // "register" pins the caller's pages for the duration of the call (hipHostRegister) and copies straight from / to them; it is
 // kept as a measurable alternative (pinning 9.6 GB costs more than it saves on this host, profiles/xfer_bench.py).
-#include <atomic>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <thread>
-#include <vector>
 
 #include <sched.h>
 
 #include "sd_internal.hpp"
-
-struct sd_xfer_team {
-  std::vector<std::thread> workers;
-  std::mutex mu;
-  std::condition_variable cv_work, cv_done;
-  char *dst = nullptr;
-  const char *src = nullptr;
-  size_t bytes = 0;
-  uint64_t generation = 0;
-  int pending = 0;
-  bool stop = false;
-  int nthreads = 1;
-
-  explicit sd_xfer_team(int n) : nthreads(n) {
-    try {
-      for (int t = 1; t < n; ++t) workers.emplace_back([this, t] { loop(t); });
-    } catch (...) {            // a destructor is not run for a half-built object: stop and join what did start, then hand the failure on
-      { std::lock_guard<std::mutex> lk(mu); stop = true; }
-      cv_work.notify_all();
-      for (auto &w : workers) w.join();
-      throw;
-    }
-  }
-  ~sd_xfer_team() {
-    { std::lock_guard<std::mutex> lk(mu); stop = true; }
-    cv_work.notify_all();
-    for (auto &w : workers) w.join();
-  }
-  static void slice(char *d, const char *s, size_t bytes, int t, int n) {
-    // page-aligned slices so that two threads never fault the same page
-    const size_t per = ((bytes / (size_t)n) + 4095) & ~(size_t)4095;
-    const size_t lo = std::min(bytes, per * (size_t)t), hi = std::min(bytes, lo + per);
-    if (hi > lo) std::memcpy(d + lo, s + lo, hi - lo);
-  }
-  void loop(int t) {
-    uint64_t seen = 0;
-    for (;;) {
-      std::unique_lock<std::mutex> lk(mu);
-      cv_work.wait(lk, [&] { return stop || generation != seen; });
-      if (stop) return;
-      seen = generation;
-      char *d = dst; const char *s = src; const size_t b = bytes;
-      lk.unlock();
-      slice(d, s, b, t, nthreads);
-      lk.lock();
-      if (--pending == 0) cv_done.notify_one();
-    }
-  }
-  // dst[0..bytes) <- src[0..bytes) by the whole team (the caller is member 0); returns when done
-  void copy(void *d, const void *s, size_t b) {
-    if (nthreads == 1 || b < ((size_t)1 << 20)) { std::memcpy(d, s, b); return; }
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      dst = (char *)d; src = (const char *)s; bytes = b;
-      pending = nthreads - 1;
-      ++generation;
-    }
-    cv_work.notify_all();
-    slice((char *)d, (const char *)s, b, 0, nthreads);
-    std::unique_lock<std::mutex> lk(mu);
-    cv_done.wait(lk, [&] { return pending == 0; });
-  }
-};
+#include "xfer_team.hpp"   // sd_xfer_team: the copy team (standard library only; tests/xfer_team_host.cpp runs it on the host)
 
 namespace {
 
