@@ -103,66 +103,6 @@ __device__ __forceinline__ int64_t rank_g(const sd_dev_model &dm, uint64_t s) {
   return idx;
 }
 
-// Rows of one site pair bi < bj (0-based bits) whose two sites differ, and their partner rows s' = s with the two sites exchanged
-// (kernels_pairs.hip, kernels_dimer.hip).  MODE as k_current: 1 tiled sector plan, 0 sector plan without tiles, 2 full basis.
-// rank_shift: |idx(s) - idx(s')| in the combinadic order (MODE 0).  Moving one up spin from bj down to bi leaves r_k (the ups still
-// to place at site k) as it is below bi and above bj and lowers it by one in between, so only the terms of sites bi..bj of rank_g's
-// sum change:
-//   d = C(L-1-bi, r-1) + sum_{bi<b<bj, b down} [C(L-1-b, r_b-1) - C(L-1-b, r_b-2)] - C(L-1-bj, r_bj-2),
-// C(n, -1) = 0, r = nup - popcount(s below bi) >= 1.  The walk reads the sites below bi and strictly between bi and bj only, which
-// s and s' share, so it serves both orientations: the row with bj up lies d rows AFTER the one with bi up.
-// lbin[n * K + k] = C(n, k), n < L, k < K = nup + 1 (the callers' LDS copy of dm.binom).
-__device__ __forceinline__ int64_t rank_shift(const sd_dev_model &dm, const int64_t *lbin, int K, uint64_t s, int bi, int bj) {
-  int r = dm.nup - __popcll(s & (((uint64_t)1 << bi) - 1));
-  int64_t d = lbin[(dm.L - 1 - bi) * K + r - 1];
-  for (int b = bi + 1; b < bj; ++b) {
-    if ((s >> b) & 1) { --r; continue; }
-    const int64_t *row = lbin + (dm.L - 1 - b) * K;
-    d += row[r - 1];
-    if (r >= 2) d -= row[r - 2];
-  }
-  if (r >= 2) d -= lbin[(dm.L - 1 - bj) * K + r - 2];
-  return d;
-}
-// MODES 1 and 2 are symmetric in the orientation: the plan's own rank of s' (two cached loads), or idx ^ mask.
-template <int MODE>
-__device__ __forceinline__ int64_t partner_sym(const sd_dev_model &dm, uint64_t s, int64_t idx, uint64_t mask) {
-  if (MODE == 2) return idx ^ (int64_t)mask;
-  const uint64_t t = s ^ mask;
-  return dm.addr[(uint32_t)t & (((uint32_t)1 << dm.p) - 1u)] + (int64_t)dm.suf_rank[t >> dm.p];
-}
-// site bj up and site bi down in s
-template <int MODE>
-__device__ __forceinline__ int64_t pair_partner(const sd_dev_model &dm, const int64_t *lbin, int K, uint64_t s, int64_t idx, int bi,
-                                                int bj) {
-  if (MODE != 0) return partner_sym<MODE>(dm, s, idx, ((uint64_t)1 << bi) | ((uint64_t)1 << bj));
-  return idx - rank_shift(dm, lbin, K, s, bi, bj);
-}
-// either orientation: the two sites differ in s
-template <int MODE>
-__device__ __forceinline__ int64_t bond_partner(const sd_dev_model &dm, const int64_t *lbin, int K, uint64_t s, int64_t idx, int bi,
-                                                int bj) {
-  if (MODE != 0) return partner_sym<MODE>(dm, s, idx, ((uint64_t)1 << bi) | ((uint64_t)1 << bj));
-  const int64_t d = rank_shift(dm, lbin, K, s, bi, bj);
-  return ((s >> bj) & 1) ? idx - d : idx + d;
-}
-
-// Row of an arbitrary configuration t of the basis (kernels_opstring.hip).  MODE as above: 2 the configuration itself; 1 the plan's
-// own rank addr[prefix of t] + suf_rank[suffix of t], two cached loads; 0 the combinadic rank walked over the caller's LDS copy of
-// the binomials, lbin[n * K + k] = C(n, k), n < L, k < K = nup + 1.  t must have nup bits set below bit L (MODES 0 and 1).
-template <int MODE>
-__device__ __forceinline__ int64_t config_row(const sd_dev_model &dm, const int64_t *lbin, int K, uint64_t t) {
-  if (MODE == 2) return (int64_t)t;
-  if (MODE == 1) return dm.addr[(uint32_t)t & (((uint32_t)1 << dm.p) - 1u)] + (int64_t)dm.suf_rank[t >> dm.p];
-  int64_t idx = 0;
-  int r = dm.nup;
-  for (int b = 0; b < dm.L && r > 0; ++b) {
-    if ((t >> b) & 1) --r;
-    else idx += lbin[(dm.L - 1 - b) * K + r - 1];
-  }
-  return idx;
-}
-
 // ---- epilogue: what is stored for row `row` given acc = (H psi)[row] ----
 struct EpiSums { double s0, s1; };
 

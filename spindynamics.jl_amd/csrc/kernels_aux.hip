@@ -142,6 +142,7 @@ __device__ __forceinline__ void obs_row(const sd_dev_model &dm, uint64_t s, cons
   }
 }
 
+// Not the shared row walk (for_rows, gather_common.hpp): dm.p at run time, a blockDim.x stride, dm.row_lo for sharded full bases.
 template <int NC, int MODE>
 __global__ __launch_bounds__(256) void k_obs(sd_dev_model dm, const double *__restrict__ psi, int c0, int cn,
                                              double *__restrict__ partials) {

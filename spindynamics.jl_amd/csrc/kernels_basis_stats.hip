@@ -5,8 +5,8 @@
 //   counting  : P[k][m] = sum_s w_s [popcount(s & mask_k) = m] for K masks.  Grid (mask chunk, row block), the chunk the FAST index as
 //               in k_pairs, so the workgroups in flight together read the same rows.  A chunk holds consecutive masks whose reachable
 //               bins fit SD_COUNT_LDS_BINS; every thread owns a private histogram in LDS, bins[bin * 256 + tid]: the bank is a function
-//               of tid alone and the read-modify-write needs no atomic.  Row configurations (MODE) as k_pairs: 1 tile prefix + suffix
-//               table, 0 unrank_g, 2 the row.
+//               of tid alone and the read-modify-write needs no atomic.  Rows and their configurations (MODE) by for_rows
+//               (gather_common.hpp): 1 tile prefix + suffix table, 0 unrank_g, 2 the row.
 //   snapshots : rows drawn from w / sum w.  Fixed chunks of SD_SAMPLE_CHUNK consecutive rows: chunk weights (one wave per chunk, fixed
 //               order), a two-level sequential scan of them that is monotone non-decreasing, then per shot a binary search of the scan
 //               and a walk of one chunk in row order.  Nothing depends on the tile plan.
@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "device_common.hpp"
+#include "gather_common.hpp"
 #include "randn.hpp"
 
 using namespace sd_dev;
@@ -166,20 +166,7 @@ __global__ __launch_bounds__(256) void k_count(sd_dev_model dm, const double *__
       mine[b * 256] += w;
     }
   };
-  if (MODE == 1) {
-    for (int t = blockIdx.y; t < dm.n_tiles; t += gridDim.y) {
-      const uint32_t P = dm.tile_prefix[t];
-      const int64_t base = dm.tile_base[t];
-      const int t2 = dm.nup - __popc(P);
-      const int len = (int)binom_g(dm, dm.LS, t2);
-      const uint16_t *__restrict__ sufS = dm.suf_states + dm.suf_off[t2];
-      for (int i = threadIdx.x; i < len; i += 256) row((uint64_t)P | ((uint64_t)sufS[i] << dm.p), base + i);
-    }
-  } else {
-    const int64_t stride = (int64_t)gridDim.y * 256;
-    for (int64_t idx = (int64_t)blockIdx.y * 256 + threadIdx.x; idx < dm.n_local; idx += stride)
-      row(MODE == 2 ? (uint64_t)idx : unrank_g(dm, idx), idx);
-  }
+  for_rows<MODE>(dm, blockIdx.y, gridDim.y, row);
   __syncthreads();
   // wave v sums bins v, v + 4, ...: four columns per lane in thread order, then the lanes
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -207,16 +194,11 @@ void count_launch(int mode, dim3 grid, size_t shmem, hipStream_t st, const sd_de
                   const int32_t *chunk_first, double *partials) {
   // a workgroup's histogram may exceed the 64 KiB a kernel gets without asking
   const int budget = SD_COUNT_LDS_BINS * 256 * (int)sizeof(double);
-  if (mode == 1) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_count<NC, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, budget);
-    hipLaunchKernelGGL((k_count<NC, 1>), grid, dim3(256), shmem, st, dm, psi, cm, chunk_first, partials);
-  } else if (mode == 2) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_count<NC, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, budget);
-    hipLaunchKernelGGL((k_count<NC, 2>), grid, dim3(256), shmem, st, dm, psi, cm, chunk_first, partials);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_count<NC, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, budget);
-    hipLaunchKernelGGL((k_count<NC, 0>), grid, dim3(256), shmem, st, dm, psi, cm, chunk_first, partials);
-  }
+  sd_with_mode(mode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_count<NC, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, budget);
+    hipLaunchKernelGGL((k_count<NC, MODE>), grid, dim3(256), shmem, st, dm, psi, cm, chunk_first, partials);
+  });
 }
 
 // ---- snapshots ----
@@ -409,9 +391,9 @@ int sd_launch_counting_statistics(sd_ctx *ctx, const sd_model *m, int dtype, con
   const sd_cmask *cm_dev = (const sd_cmask *)tab.p;
   const int32_t *first_dev = (const int32_t *)((const unsigned char *)tab.p + cm_bytes);
   const int32_t *dst_dev = first_dev + (2 * nchunks + 1);
-  const int mode = dm.nup < 0 ? 2 : (m->p >= 0 && dm.n_tiles > 0) ? 1 : 0;
-  const int64_t nb64 = mode == 1 ? (int64_t)dm.n_tiles : (dm.n_local + 255) / 256;
-  const unsigned nb = (unsigned)std::min<int64_t>(nb64, SD_COUNT_MAX_BLOCKS);
+  const sd_gather_grid g = sd_gather_grid_of(m, SD_COUNT_MAX_BLOCKS, SD_COUNT_MAX_BLOCKS);
+  const int mode = g.mode;
+  const unsigned nb = g.nb;
   rc = sd_ensure_partials(ctx, (size_t)total * nb);
   if (rc) return rc;
   const size_t shmem = (size_t)*std::max_element(cbins.begin(), cbins.end()) * 256 * sizeof(double);

@@ -11,8 +11,8 @@
 //   bracket : sum_s conj(bra[s]) (J_w ket)[s]            (bra Float64 or ComplexF64, ket ComplexF64) WITHOUT writing J_w ket --
 //             the per-time-point measurement of the typicality driver: two read streams plus the gathers.  Per-thread sums,
 //             a fixed-order block reduction, then sd_reduce_pairs over the blocks: no atomics, the same call gives the same bits.
-// Where the row's configuration comes from (MODE): 1 the tile's prefix and the suffix table of a tiled sector plan (as
-// k_site_project), 0 unrank_g of the row (sector plans without tiles), 2 the row index itself (full basis).  Partner rows in a
+// Rows and their configurations (MODE) by for_rows (gather_common.hpp): 1 the tile's prefix and the suffix table of a tiled sector
+// plan, 0 unrank_g of the row (sector plans without tiles), 2 the row index itself (full basis).  Partner rows in a
 // sector: the leading chain bonds (b, b+1) by the closed form of the combinadic order,
 //     idx +- C(L - b - 1, u),   u = ups among the sites above b + 1,   + when site b is the up one,
 // with the binomials in LDS; every other bond by the rank walk, as k_apply_short / k_apply_generic do.
@@ -20,7 +20,7 @@
 
 #include <algorithm>
 
-#include "device_common.hpp"
+#include "gather_common.hpp"
 
 using namespace sd_dev;
 
@@ -67,10 +67,7 @@ __global__ __launch_bounds__(256) void k_current(sd_dev_model dm, const double *
   double *red = reinterpret_cast<double *>(smem);            // 32 doubles
   int64_t *lbin = reinterpret_cast<int64_t *>(red + 32);     // lbin[n * K + k] = C(n, k), n < L, k <= nup (sector plans with chain bonds)
   const int K = (dm.nup > 0 ? dm.nup : 0) + 1;
-  if (MODE != 2 && dm.nn_hops > 0) {
-    for (int k = threadIdx.x; k < dm.L * K; k += 256) lbin[k] = dm.binom[(k / K) * (SD_MAX_L + 1) + (k % K)];
-    __syncthreads();
-  }
+  if (MODE != 2 && dm.nn_hops > 0) fill_lbin<0>(dm, lbin, K);   // the chain bonds' closed form reads it in MODE 1 too
   double sr = 0.0, si = 0.0;
   auto row = [&](uint64_t s, int64_t idx) {
     const double2 a = current_row<NCK, MODE>(dm, vec, wt, lbin, K, s, idx);
@@ -87,32 +84,22 @@ __global__ __launch_bounds__(256) void k_current(sd_dev_model dm, const double *
       si += bv * j.y;
     }
   };
-  if (MODE == 1) {
-    for (int t = blockIdx.x; t < dm.n_tiles; t += gridDim.x) {
-      const uint32_t P = dm.tile_prefix[t];
-      const int64_t base = dm.tile_base[t];
-      const int t2 = dm.nup - __popc(P);
-      const int len = (int)binom_g(dm, dm.LS, t2);
-      const uint16_t *__restrict__ sufS = dm.suf_states + dm.suf_off[t2];
-      for (int i = threadIdx.x; i < len; i += 256) row((uint64_t)P | ((uint64_t)sufS[i] << dm.p), base + i);
-    }
-  } else {
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < dm.n_local; idx += stride)
-      row(MODE == 2 ? (uint64_t)idx : unrank_g(dm, idx), idx);
-  }
+  for_rows<MODE>(dm, blockIdx.x, gridDim.x, row);
   if (BRACKET) {
     block_reduce2(sr, si, red);
     if (threadIdx.x == 0) { partials[2 * (size_t)blockIdx.x] = sr; partials[2 * (size_t)blockIdx.x + 1] = si; }
   }
 }
 
+#define SD_CURRENT_TILE_BLOCKS 4096      // tiled plans: workgroups, one tile at a time each
+#define SD_CURRENT_ROW_BLOCKS 8192       // blocks of 256 rows (per-row plans, full basis)
+
 template <int NC, bool BRACKET>
 void launch_mode(int mode, unsigned nb, size_t shmem, hipStream_t st, const sd_dev_model &dm, const double *vec, const double *bra,
                  const double *wt, double2 *out, double *partials) {
-  if (mode == 1) hipLaunchKernelGGL((k_current<NC, BRACKET, 1>), dim3(nb), dim3(256), shmem, st, dm, vec, bra, wt, out, partials);
-  else if (mode == 2) hipLaunchKernelGGL((k_current<NC, BRACKET, 2>), dim3(nb), dim3(256), shmem, st, dm, vec, bra, wt, out, partials);
-  else hipLaunchKernelGGL((k_current<NC, BRACKET, 0>), dim3(nb), dim3(256), shmem, st, dm, vec, bra, wt, out, partials);
+  sd_with_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL((k_current<NC, BRACKET, decltype(M)::value>), dim3(nb), dim3(256), shmem, st, dm, vec, bra, wt, out, partials);
+  });
 }
 
 }  // namespace
@@ -122,18 +109,17 @@ void launch_mode(int mode, unsigned nb, size_t shmem, hipStream_t st, const sd_d
 // Queued on the context's stream.
 int sd_launch_current(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, const double *wt_dev, void *out,
                       double *dst) {
-  if (!m->dev_ready) return sd_set_err(ctx, SD_EARG, "model has no device tables (created without a context)");
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "the spin current needs an unsharded model");
+  if (int rc = sd_gather_check(ctx, m, dtype, "the spin current needs")) return rc;
   const sd_dev_model &dm = m->dm;
   const bool bracket = out == nullptr;
   if (dm.n_local == 0) {      // no rows: the bracket is zero
     if (bracket) SD_HIP(ctx, hipMemsetAsync(dst, 0, 2 * sizeof(double), ctx->stream));
     return SD_OK;
   }
-  const int mode = dm.nup < 0 ? 2 : (m->p >= 0 && dm.n_tiles > 0) ? 1 : 0;
-  int64_t nb64 = mode == 1 ? std::min<int64_t>(dm.n_tiles, 4096) : std::min<int64_t>((dm.n_local + 255) / 256, 8192);
-  const unsigned nb = (unsigned)std::max<int64_t>(nb64, 1);
+  const sd_gather_grid g = sd_gather_grid_of(m, SD_CURRENT_TILE_BLOCKS, SD_CURRENT_ROW_BLOCKS);
+  const int mode = g.mode;
+  const unsigned nb = std::max(g.nb, 1u);
+  // not g.lbin_bytes: the chain bonds read the binomials in MODE 1 as well, and the region is sized in every mode
   const size_t shmem = 32 * sizeof(double) + (size_t)dm.L * (size_t)((dm.nup > 0 ? dm.nup : 0) + 1) * sizeof(int64_t);
   if (bracket) { int rc = sd_ensure_partials(ctx, 2 * (size_t)nb + 2 * SD_RED_STAGE_BLOCKS); if (rc) return rc; }
   const double *v = (const double *)vec, *b = (const double *)bra;

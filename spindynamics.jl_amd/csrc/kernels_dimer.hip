@@ -12,14 +12,14 @@
 // workgroups in flight together read the same rows and psi is streamed from memory about once, not once per tile.
 // Only the tiles ca <= cb are summed; the host fills the other triangle with the conjugate (and inside a diagonal tile uses
 // a <= b only), so the matrix is Hermitian to the bit.
-// Row configurations and partner rows (MODE) as k_pairs; the partner of either orientation is bond_partner (device_common.hpp).
+// Rows and their configurations (MODE) by for_rows, the partner of either orientation by bond_partner (gather_common.hpp).
 // Sums: per thread, block_reduce2, block partials in ctx->d_partials, k_dimer_reduce adds them in a fixed order.  No atomics, and
 // the grid depends on the plan and B alone: the same call gives the same bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "device_common.hpp"
+#include "gather_common.hpp"
 
 using namespace sd_dev;
 
@@ -53,42 +53,14 @@ __device__ __forceinline__ void bond_value(const sd_dev_model &dm, const int64_t
   }
 }
 
-// the rows of this workgroup's share (blockIdx.y of gridDim.y), each handed to f(configuration, row)
-template <int MODE, class F>
-__device__ __forceinline__ void for_rows(const sd_dev_model &dm, F &&f) {
-  if (MODE == 1) {
-    for (int t = blockIdx.y; t < dm.n_tiles; t += gridDim.y) {
-      const uint32_t P = dm.tile_prefix[t];
-      const int64_t base = dm.tile_base[t];
-      const int t2 = dm.nup - __popc(P);
-      const int len = (int)binom_g(dm, dm.LS, t2);
-      const uint16_t *__restrict__ sufS = dm.suf_states + dm.suf_off[t2];
-      for (int i = threadIdx.x; i < len; i += 256) f((uint64_t)P | ((uint64_t)sufS[i] << dm.p), base + i);
-    }
-  } else {
-    const int64_t stride = (int64_t)gridDim.y * 256;
-    for (int64_t idx = (int64_t)blockIdx.y * 256 + threadIdx.x; idx < dm.n_local; idx += stride)
-      f(MODE == 2 ? (uint64_t)idx : unrank_g(dm, idx), idx);
-  }
-}
-
-// the binomials of the rank walk in LDS (MODE 0 only)
-template <int MODE>
-__device__ __forceinline__ void load_lbin(const sd_dev_model &dm, int64_t *lbin, int K) {
-  if (MODE == 0) {
-    for (int k = threadIdx.x; k < dm.L * K; k += 256) lbin[k] = dm.binom[(k / K) * (SD_MAX_L + 1) + (k % K)];
-    __syncthreads();
-  }
-}
-
 template <int NC, int MODE>
 __global__ __launch_bounds__(256) void k_bond_apply(sd_dev_model dm, const double *__restrict__ psi, int pb, double cz, double cx,
                                                     double *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int64_t *lbin = reinterpret_cast<int64_t *>(smem);
   const int K = (dm.nup > 0 ? dm.nup : 0) + 1;
-  load_lbin<MODE>(dm, lbin, K);
-  for_rows<MODE>(dm, [&](uint64_t s, int64_t idx) {
+  fill_lbin<MODE>(dm, lbin, K);
+  for_rows<MODE>(dm, blockIdx.y, gridDim.y, [&](uint64_t s, int64_t idx) {
     double vr, vi = 0.0, dr, di;
     if (NC == 2) { const double2 v = ((const double2 *)psi)[idx]; vr = v.x; vi = v.y; }
     else vr = psi[idx];
@@ -106,7 +78,7 @@ __global__ __launch_bounds__(256) void k_dimer_gram(sd_dev_model dm, const doubl
   double *red = reinterpret_cast<double *>(smem);            // 32 doubles
   int64_t *lbin = reinterpret_cast<int64_t *>(red + 32);
   const int K = (dm.nup > 0 ? dm.nup : 0) + 1;
-  load_lbin<MODE>(dm, lbin, K);
+  fill_lbin<MODE>(dm, lbin, K);
   const int nc = (B + SD_DIMER_CHUNK - 1) / SD_DIMER_CHUNK;
   int ca = 0, cb = (int)blockIdx.x;
   while (cb >= nc - ca) { cb -= nc - ca; ++ca; }
@@ -123,7 +95,7 @@ __global__ __launch_bounds__(256) void k_dimer_gram(sd_dev_model dm, const doubl
 #pragma unroll
     for (int l = 0; l < SD_DIMER_CHUNK; ++l) { ar[k][l] = 0.0; ai[k][l] = 0.0; }
   }
-  for_rows<MODE>(dm, [&](uint64_t s, int64_t idx) {
+  for_rows<MODE>(dm, blockIdx.y, gridDim.y, [&](uint64_t s, int64_t idx) {
     double vr, vi = 0.0;
     if (NC == 2) { const double2 v = ((const double2 *)psi)[idx]; vr = v.x; vi = v.y; }
     else vr = psi[idx];
@@ -193,20 +165,8 @@ __global__ __launch_bounds__(256) void k_dimer_reduce(const double *__restrict__
   }
 }
 
-int dimer_mode(const sd_model *m) { return m->dm.nup < 0 ? 2 : (m->p >= 0 && m->dm.n_tiles > 0) ? 1 : 0; }
-unsigned dimer_row_blocks(const sd_model *m, int mode) {
-  const int64_t nb64 = mode == 1 ? (int64_t)m->dm.n_tiles : (m->dm.n_local + 255) / 256;
-  return (unsigned)std::min<int64_t>(nb64, SD_DIMER_MAX_BLOCKS);
-}
-size_t lbin_bytes(const sd_model *m, int mode) {
-  return mode == 0 ? (size_t)m->dm.L * (size_t)(m->dm.nup + 1) * sizeof(int64_t) : 0;
-}
-
 int check_model(sd_ctx *ctx, const sd_model *m, int dtype) {
-  if (!m->dev_ready) return sd_set_err(ctx, SD_EARG, "model has no device tables (created without a context)");
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "bond operators and dimer correlations need an unsharded model");
-  return SD_OK;
+  return sd_gather_check(ctx, m, dtype, "bond operators and dimer correlations need");
 }
 
 }  // namespace
@@ -218,20 +178,17 @@ int sd_launch_bond_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *
   if (bi < 0 || bi >= bj || bj >= m->L) return sd_set_err(ctx, SD_EINTERNAL, "bond apply: bad bond");
   const sd_dev_model &dm = m->dm;
   if (dm.n_local == 0) return SD_OK;
-  const int mode = dimer_mode(m);
-  const dim3 grid(1, dimer_row_blocks(m, mode));
-  const size_t shmem = lbin_bytes(m, mode);
+  const sd_gather_grid g = sd_gather_grid_of(m, SD_DIMER_MAX_BLOCKS, SD_DIMER_MAX_BLOCKS);
+  const dim3 grid(1, g.nb);
   const int pb = bi | (bj << 8);
   const double cz = zz * 0.25, cx = xy * 0.5;
   const double *v = (const double *)psi;
   double *o = (double *)out;
-#define SD_BOND_LAUNCH(NC, MODE) hipLaunchKernelGGL((k_bond_apply<NC, MODE>), grid, dim3(256), shmem, ctx->stream, dm, v, pb, cz, cx, o)
-  if (dtype == SD_C128) {
-    if (mode == 1) SD_BOND_LAUNCH(2, 1); else if (mode == 2) SD_BOND_LAUNCH(2, 2); else SD_BOND_LAUNCH(2, 0);
-  } else {
-    if (mode == 1) SD_BOND_LAUNCH(1, 1); else if (mode == 2) SD_BOND_LAUNCH(1, 2); else SD_BOND_LAUNCH(1, 0);
-  }
-#undef SD_BOND_LAUNCH
+  sd_with_mode(g.mode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    if (dtype == SD_C128) hipLaunchKernelGGL((k_bond_apply<2, MODE>), grid, dim3(256), g.lbin_bytes, ctx->stream, dm, v, pb, cz, cx, o);
+    else hipLaunchKernelGGL((k_bond_apply<1, MODE>), grid, dim3(256), g.lbin_bytes, ctx->stream, dm, v, pb, cz, cx, o);
+  });
   SD_HIP(ctx, hipGetLastError());
   return SD_OK;
 }
@@ -256,22 +213,21 @@ int sd_launch_dimer_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *
     SD_HIP(ctx, hipMemsetAsync(dst, 0, (size_t)ntiles * SD_DIMER_ROW * sizeof(double), ctx->stream));
     return SD_OK;
   }
-  const int mode = dimer_mode(m);
-  const unsigned nb = dimer_row_blocks(m, mode);
-  const size_t shmem = 32 * sizeof(double) + lbin_bytes(m, mode);
+  const sd_gather_grid g = sd_gather_grid_of(m, SD_DIMER_MAX_BLOCKS, SD_DIMER_MAX_BLOCKS);
+  const unsigned nb = g.nb;
+  const size_t shmem = 32 * sizeof(double) + g.lbin_bytes;
   rc = sd_ensure_partials(ctx, (size_t)ntiles * nb * SD_DIMER_ROW);
   if (rc) return rc;
   const dim3 grid(ntiles, nb);
   const double cz = zz * 0.25, cx = xy * 0.5;
   const double *v = (const double *)psi;
-#define SD_DIMER_LAUNCH(NC, MODE) \
-  hipLaunchKernelGGL((k_dimer_gram<NC, MODE>), grid, dim3(256), shmem, ctx->stream, dm, v, bonds_dev, B, cz, cx, ctx->d_partials)
-  if (dtype == SD_C128) {
-    if (mode == 1) SD_DIMER_LAUNCH(2, 1); else if (mode == 2) SD_DIMER_LAUNCH(2, 2); else SD_DIMER_LAUNCH(2, 0);
-  } else {
-    if (mode == 1) SD_DIMER_LAUNCH(1, 1); else if (mode == 2) SD_DIMER_LAUNCH(1, 2); else SD_DIMER_LAUNCH(1, 0);
-  }
-#undef SD_DIMER_LAUNCH
+  sd_with_mode(g.mode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    if (dtype == SD_C128)
+      hipLaunchKernelGGL((k_dimer_gram<2, MODE>), grid, dim3(256), shmem, ctx->stream, dm, v, bonds_dev, B, cz, cx, ctx->d_partials);
+    else
+      hipLaunchKernelGGL((k_dimer_gram<1, MODE>), grid, dim3(256), shmem, ctx->stream, dm, v, bonds_dev, B, cz, cx, ctx->d_partials);
+  });
   hipLaunchKernelGGL(k_dimer_reduce, dim3(ntiles), dim3(256), 0, ctx->stream, ctx->d_partials, (int)nb, dst);
   SD_HIP(ctx, hipGetLastError());
   return SD_OK;

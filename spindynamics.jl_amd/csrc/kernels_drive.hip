@@ -6,16 +6,16 @@
 // d(s), -ffp-contract=off, the selection idea of diag_of's list-order form: a sequential sum from 0.0 of the site terms i = 0..L-1, each
 // +W_i/2 (site up) or -W_i/2, then of the bond terms in list order, each +V_b/4 (parallel) or -V_b/4.  The table holds the halves and
 // quarters, which are exact, so every term is selected, not multiplied.  Without site weights the site loop is skipped.
-// Row configurations (MODE), as k_count / k_pairs: 1 the tile's prefix and the suffix table of a tiled sector plan, 0 unrank_g of the
-// row, 2 the row index (full basis).  MODE 1 splits the sum as diag_head / diag_tail do: its leading terms depend on the prefix alone
-// -- the site terms of sites 0..p-1, or (no site weights) the leading bonds that lie inside the prefix -- and are formed once per tile;
-// every row continues the same sequential sum, so the bits are those of the undivided loop.
+// Row configurations (MODE) of gather_common.hpp: 1 the tile's prefix and the suffix table of a tiled sector plan (for_tiles), 0
+// unrank_g of the row, 2 the row index (full basis).  MODE 1 splits the sum as diag_head / diag_tail do: its leading terms depend on
+// the prefix alone -- the site terms of sites 0..p-1, or (no site weights) the leading bonds that lie inside the prefix -- and are
+// formed once per tile; every row continues the same sequential sum, so the bits are those of the undivided loop.
 // Sums: per thread, block_reduce2, one pair per block in ctx->d_partials, sd_reduce_pairs -- as k_epilogue_only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "device_common.hpp"
+#include "gather_common.hpp"
 
 using namespace sd_dev;
 
@@ -80,12 +80,7 @@ __global__ __launch_bounds__(256) void k_drive_epilogue(sd_dev_model dm, sd_driv
     epilogue<NC>(epi, ea, r, acc, own, out_, sums);
   };
   if (MODE == 1) {
-    for (int t = blockIdx.x; t < dm.n_tiles; t += gridDim.x) {
-      const uint32_t P = dm.tile_prefix[t];
-      const int64_t base = dm.tile_base[t];
-      const int t2 = dm.nup - __popc(P);
-      const int len = (int)binom_g(dm, dm.LS, t2);
-      const uint16_t *__restrict__ sufS = dm.suf_states + dm.suf_off[t2];
+    for_tiles(dm, blockIdx.x, gridDim.x, [&](uint32_t P, int64_t base, int len, const uint16_t *__restrict__ sufS) {
       const double d0 = tb.has_sites ? drive_sites(tb, (uint64_t)P, 0, dm.p, 0.0) : drive_bonds(tb, (uint64_t)P, 0, head_bonds, 0.0);
       for (int i = threadIdx.x; i < len; i += 256) {
         const uint64_t s = (uint64_t)P | ((uint64_t)sufS[i] << dm.p);
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(256) void k_drive_epilogue(sd_dev_model dm, sd_driv
         else d = drive_bonds(tb, s, head_bonds, tb.n_bonds, d);
         row(base + i, d);
       }
-    }
+    });
   } else {
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < dm.n_local; idx += stride) {
@@ -115,9 +110,9 @@ template <int NC>
 void launch_drive(int mode, unsigned nb, hipStream_t st, const sd_dev_model &dm, const sd_drive_table &tb, int head_bonds, int epi,
                   const sd_epi_args &ea, double *out, const double *h, const double *psi, double *partials) {
   const dim3 grid(nb), blk(256);
-  if (mode == 1) hipLaunchKernelGGL((k_drive_epilogue<NC, 1>), grid, blk, 0, st, dm, tb, head_bonds, epi, ea, out, h, psi, partials);
-  else if (mode == 2) hipLaunchKernelGGL((k_drive_epilogue<NC, 2>), grid, blk, 0, st, dm, tb, head_bonds, epi, ea, out, h, psi, partials);
-  else hipLaunchKernelGGL((k_drive_epilogue<NC, 0>), grid, blk, 0, st, dm, tb, head_bonds, epi, ea, out, h, psi, partials);
+  sd_with_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL((k_drive_epilogue<NC, decltype(M)::value>), grid, blk, 0, st, dm, tb, head_bonds, epi, ea, out, h, psi, partials);
+  });
 }
 
 }  // namespace
@@ -138,9 +133,9 @@ int sd_launch_drive_epilogue(sd_ctx *ctx, const sd_model *m, int dtype, void *ou
     if (sums) SD_HIP(ctx, hipMemsetAsync(ea.sums_dst ? ea.sums_dst : ctx->d_scalars, 0, 2 * sizeof(double), ctx->stream));
     return SD_OK;
   }
-  const int mode = dm.nup < 0 ? 2 : (m->p >= 0 && dm.n_tiles > 0) ? 1 : 0;
-  const int64_t nb64 = mode == 1 ? (int64_t)dm.n_tiles : (dm.n_local + 255) / 256;
-  const int64_t nb = std::min<int64_t>(nb64, mode == 1 ? SD_DRIVE_TILE_BLOCKS : SD_DRIVE_ROW_BLOCKS);
+  const sd_gather_grid g = sd_gather_grid_of(m, SD_DRIVE_TILE_BLOCKS, SD_DRIVE_ROW_BLOCKS);
+  const int mode = g.mode;
+  const int64_t nb = g.nb;
   int head_bonds = 0;
   if (mode == 1 && !table.has_sites)
     while (head_bonds < table.n_bonds && (table.bits[head_bonds] & 255) < dm.p && (table.bits[head_bonds] >> 8) < dm.p) ++head_bonds;

@@ -10,14 +10,15 @@
 //   write   : out[s] = (J psi)[s]                  (psi Float64 or ComplexF64, out ComplexF64)
 //   bracket : sum_s conj(bra[s]) (J ket)[s]        (bra Float64 or ComplexF64, ket ComplexF64) without writing J ket.  Per-thread sums,
 //             block_reduce2, then sd_reduce_pairs over the blocks: no atomics, the grid depends on the plan alone.
-// Row configurations (MODE) as k_current: 1 tile prefix and suffix table, 0 unrank_g of the row, 2 the row index.  Partner rows by
-// bond_partner (device_common.hpp): the plan's tables, the local rank walk with the binomials in LDS, or idx ^ mask.
+// Rows and their configurations (MODE) by for_rows (gather_common.hpp): 1 tile prefix and suffix table, 0 unrank_g of the row, 2 the
+// row index.  Partner rows by bond_partner (same header): the plan's tables, the local rank walk with the binomials in LDS, or
+// idx ^ mask.
 // The group and term tables are read from global memory with wave-uniform indices (scalar loads), as k_current reads its hop list.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "device_common.hpp"
+#include "gather_common.hpp"
 
 using namespace sd_dev;
 
@@ -65,10 +66,7 @@ __global__ __launch_bounds__(256) void k_dcurrent(sd_dev_model dm, const double 
   double *red = reinterpret_cast<double *>(smem);            // 32 doubles
   int64_t *lbin = reinterpret_cast<int64_t *>(red + 32);     // lbin[n * K + k] = C(n, k), n < L, k <= nup (MODE 0: the rank walk)
   const int K = (dm.nup > 0 ? dm.nup : 0) + 1;
-  if (MODE == 0) {
-    for (int k = threadIdx.x; k < dm.L * K; k += 256) lbin[k] = dm.binom[(k / K) * (SD_MAX_L + 1) + (k % K)];
-    __syncthreads();
-  }
+  fill_lbin<MODE>(dm, lbin, K);
   double sr = 0.0, si = 0.0;
   auto row = [&](uint64_t s, int64_t idx) {
     const double2 a = dcurrent_row<NCK, MODE>(dm, vec, groups, n_groups, terms, lbin, K, s, idx);
@@ -85,35 +83,23 @@ __global__ __launch_bounds__(256) void k_dcurrent(sd_dev_model dm, const double 
       si += bv * j.y;
     }
   };
-  if (MODE == 1) {
-    for (int t = blockIdx.x; t < dm.n_tiles; t += gridDim.x) {
-      const uint32_t P = dm.tile_prefix[t];
-      const int64_t base = dm.tile_base[t];
-      const int t2 = dm.nup - __popc(P);
-      const int len = (int)binom_g(dm, dm.LS, t2);
-      const uint16_t *__restrict__ sufS = dm.suf_states + dm.suf_off[t2];
-      for (int i = threadIdx.x; i < len; i += 256) row((uint64_t)P | ((uint64_t)sufS[i] << dm.p), base + i);
-    }
-  } else {
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < dm.n_local; idx += stride)
-      row(MODE == 2 ? (uint64_t)idx : unrank_g(dm, idx), idx);
-  }
+  for_rows<MODE>(dm, blockIdx.x, gridDim.x, row);
   if (BRACKET) {
     block_reduce2(sr, si, red);
     if (threadIdx.x == 0) { partials[2 * (size_t)blockIdx.x] = sr; partials[2 * (size_t)blockIdx.x + 1] = si; }
   }
 }
 
+#define SD_DCURRENT_TILE_BLOCKS 4096     // tiled plans: workgroups, as k_current's
+#define SD_DCURRENT_ROW_BLOCKS 8192      // blocks of 256 rows (per-row plans, full basis), as k_current's
+
 template <int NC, bool BRACKET>
 void launch_mode(int mode, unsigned nb, size_t shmem, hipStream_t st, const sd_dev_model &dm, const double *vec, const double *bra,
                  const sd_dgroup *groups, int n_groups, const sd_dterm_dev *terms, double2 *out, double *partials) {
-  if (mode == 1)
-    hipLaunchKernelGGL((k_dcurrent<NC, BRACKET, 1>), dim3(nb), dim3(256), shmem, st, dm, vec, bra, groups, n_groups, terms, out, partials);
-  else if (mode == 2)
-    hipLaunchKernelGGL((k_dcurrent<NC, BRACKET, 2>), dim3(nb), dim3(256), shmem, st, dm, vec, bra, groups, n_groups, terms, out, partials);
-  else
-    hipLaunchKernelGGL((k_dcurrent<NC, BRACKET, 0>), dim3(nb), dim3(256), shmem, st, dm, vec, bra, groups, n_groups, terms, out, partials);
+  sd_with_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL((k_dcurrent<NC, BRACKET, decltype(M)::value>), dim3(nb), dim3(256), shmem, st, dm, vec, bra, groups, n_groups, terms,
+                       out, partials);
+  });
 }
 
 }  // namespace
@@ -123,9 +109,7 @@ void launch_mode(int mode, unsigned nb, size_t shmem, hipStream_t st, const sd_d
 // (n_groups == 0: the empty list, J = 0).  Launch caps as sd_launch_current.  Queued on the context's stream.
 int sd_launch_dcurrent(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, const sd_dgroup *groups_dev,
                        int n_groups, const sd_dterm_dev *terms_dev, void *out, double *dst) {
-  if (!m->dev_ready) return sd_set_err(ctx, SD_EARG, "model has no device tables (created without a context)");
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "the energy current needs an unsharded model");
+  if (int rc = sd_gather_check(ctx, m, dtype, "the energy current needs")) return rc;
   const sd_dev_model &dm = m->dm;
   const bool bracket = out == nullptr;
   if (dm.n_local == 0 || n_groups == 0) {      // no rows, or no terms: a zero bracket, a zero vector
@@ -133,10 +117,10 @@ int sd_launch_dcurrent(sd_ctx *ctx, const sd_model *m, int dtype, const void *ve
     else if (dm.n_local > 0) SD_HIP(ctx, hipMemsetAsync(out, 0, 2 * sizeof(double) * (size_t)dm.n_local, ctx->stream));
     return SD_OK;
   }
-  const int mode = dm.nup < 0 ? 2 : (m->p >= 0 && dm.n_tiles > 0) ? 1 : 0;
-  const int64_t nb64 = mode == 1 ? std::min<int64_t>(dm.n_tiles, 4096) : std::min<int64_t>((dm.n_local + 255) / 256, 8192);
-  const unsigned nb = (unsigned)std::max<int64_t>(nb64, 1);
-  const size_t shmem = 32 * sizeof(double) + (mode == 0 ? (size_t)dm.L * (size_t)(dm.nup + 1) * sizeof(int64_t) : 0);
+  const sd_gather_grid g = sd_gather_grid_of(m, SD_DCURRENT_TILE_BLOCKS, SD_DCURRENT_ROW_BLOCKS);
+  const int mode = g.mode;
+  const unsigned nb = std::max(g.nb, 1u);
+  const size_t shmem = 32 * sizeof(double) + g.lbin_bytes;
   if (bracket) { int rc = sd_ensure_partials(ctx, 2 * (size_t)nb + 2 * SD_RED_STAGE_BLOCKS); if (rc) return rc; }
   const double *v = (const double *)vec, *b = (const double *)bra;
   double2 *o = (double2 *)out;

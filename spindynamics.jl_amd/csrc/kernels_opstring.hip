@@ -15,14 +15,14 @@
 //                     the FAST grid index; per-thread accumulators, block_reduce2, block partials in ctx->d_partials (one list of
 //                     pairs per operator), sd_reduce_pairs_batched adds them in a fixed order.  No atomics; the grid depends on the
 //                     plan and K alone: the same call gives the same bits.
-// Row configurations (MODE) as k_dcurrent: 1 the tile's prefix and the suffix table of a tiled sector plan, 0 unrank_g of the row, 2
-// the row index (full basis).  Source rows by config_row (device_common.hpp).  The group and term tables are read from global memory
-// with wave-uniform indices (scalar loads).
+// Rows and their configurations (MODE) by for_rows (gather_common.hpp): 1 the tile's prefix and the suffix table of a tiled sector
+// plan, 0 unrank_g of the row, 2 the row index (full basis).  Source rows by config_row (same header).  The group and term tables are
+// read from global memory with wave-uniform indices (scalar loads).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "device_common.hpp"
+#include "gather_common.hpp"
 
 using namespace sd_dev;
 
@@ -32,31 +32,6 @@ namespace {
 #define SD_OPS_RED_BLOCKS 2048          // expectations: row blocks (grid.y), tiles or blocks of 256 rows, as k_pairs
 #define SD_OPS_TILE_BLOCKS 4096         // write form, tiled plans: workgroups, as k_dcurrent
 #define SD_OPS_ROW_BLOCKS 8192          // write form, blocks of 256 rows (per-row plans, full basis), as k_dcurrent
-
-// lbin[n * K + k] = C(n, k), n < L, k < K = nup + 1 (MODE 0)
-__device__ __forceinline__ void ops_fill_lbin(const sd_dev_model &dm, int64_t *lbin, int K) {
-  for (int k = threadIdx.x; k < dm.L * K; k += 256) lbin[k] = dm.binom[(k / K) * (SD_MAX_L + 1) + (k % K)];
-  __syncthreads();
-}
-
-// row(s, idx) for this workgroup's share of the rows: workgroup `blk` of `nblk`
-template <int MODE, class F>
-__device__ __forceinline__ void ops_rows(const sd_dev_model &dm, unsigned blk, unsigned nblk, F &&row) {
-  if (MODE == 1) {
-    for (int t = blk; t < dm.n_tiles; t += nblk) {
-      const uint32_t P = dm.tile_prefix[t];
-      const int64_t base = dm.tile_base[t];
-      const int t2 = dm.nup - __popc(P);
-      const int len = (int)binom_g(dm, dm.LS, t2);
-      const uint16_t *__restrict__ sufS = dm.suf_states + dm.suf_off[t2];
-      for (int i = threadIdx.x; i < len; i += 256) row((uint64_t)P | ((uint64_t)sufS[i] << dm.p), base + i);
-    }
-  } else {
-    const int64_t stride = (int64_t)nblk * 256;
-    for (int64_t idx = (int64_t)blk * 256 + threadIdx.x; idx < dm.n_local; idx += stride)
-      row(MODE == 2 ? (uint64_t)idx : unrank_g(dm, idx), idx);
-  }
-}
 
 // (O psi)[s] over groups[g0 .. g1) for row idx with configuration s.  NCI = 1: psi is real; WANT_IM = false: the imaginary part is
 // not formed (a Float64 output: every ch_im is 0).
@@ -100,8 +75,8 @@ __global__ __launch_bounds__(256) void k_opstring(sd_dev_model dm, const double 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int64_t *lbin = reinterpret_cast<int64_t *>(smem);
   const int K = (dm.nup > 0 ? dm.nup : 0) + 1;
-  if (MODE == 0) ops_fill_lbin(dm, lbin, K);
-  ops_rows<MODE>(dm, blockIdx.x, gridDim.x, [&](uint64_t s, int64_t idx) {
+  fill_lbin<MODE>(dm, lbin, K);
+  for_rows<MODE>(dm, blockIdx.x, gridDim.x, [&](uint64_t s, int64_t idx) {
     double2 a = opstring_row<NCI, NCO == 2, MODE>(dm, psi, groups, 0, n_groups, terms, lbin, K, s, idx);
     if (NCO == 2) {
       if (FUSED) {
@@ -129,7 +104,7 @@ __global__ __launch_bounds__(256) void k_opstring_expect(sd_dev_model dm, const 
   double *red = reinterpret_cast<double *>(smem);            // 32 doubles
   int64_t *lbin = reinterpret_cast<int64_t *>(red + 32);
   const int K = (dm.nup > 0 ? dm.nup : 0) + 1;
-  if (MODE == 0) ops_fill_lbin(dm, lbin, K);
+  fill_lbin<MODE>(dm, lbin, K);
   const int c0 = blockIdx.x * SD_OPS_CHUNK, cn = min(SD_OPS_CHUNK, n_ops - c0);
   int g0[SD_OPS_CHUNK], g1[SD_OPS_CHUNK];
   double ar[SD_OPS_CHUNK], ai[SD_OPS_CHUNK];
@@ -139,7 +114,7 @@ __global__ __launch_bounds__(256) void k_opstring_expect(sd_dev_model dm, const 
     g1[k] = k < cn ? op_first[c0 + k + 1] : 0;
     ar[k] = 0.0; ai[k] = 0.0;
   }
-  ops_rows<MODE>(dm, blockIdx.y, gridDim.y, [&](uint64_t s, int64_t idx) {
+  for_rows<MODE>(dm, blockIdx.y, gridDim.y, [&](uint64_t s, int64_t idx) {
     double br, bi = 0.0;
     if (NC == 2) { const double2 b = ((const double2 *)bra)[idx]; br = b.x; bi = b.y; }
     else br = bra[idx];
@@ -163,49 +138,35 @@ __global__ __launch_bounds__(256) void k_opstring_expect(sd_dev_model dm, const 
   }
 }
 
-struct OpsGrid { int mode; unsigned nb; size_t lbin_bytes; };
-OpsGrid ops_grid(const sd_model *m, bool reduction) {
-  const sd_dev_model &dm = m->dm;
-  OpsGrid g;
-  g.mode = dm.nup < 0 ? 2 : (m->p >= 0 && dm.n_tiles > 0) ? 1 : 0;
-  const int64_t nb64 = g.mode == 1 ? (int64_t)dm.n_tiles : (dm.n_local + 255) / 256;
-  const int64_t cap = reduction ? SD_OPS_RED_BLOCKS : g.mode == 1 ? SD_OPS_TILE_BLOCKS : SD_OPS_ROW_BLOCKS;
-  g.nb = (unsigned)std::max<int64_t>(std::min<int64_t>(nb64, cap), 1);
-  g.lbin_bytes = g.mode == 0 ? (size_t)dm.L * (size_t)(dm.nup + 1) * sizeof(int64_t) : 0;
-  return g;
-}
-
 template <int NCI, int NCO, bool FUSED>
-void launch_write(const OpsGrid &g, hipStream_t st, const sd_dev_model &dm, const double *psi, const sd_opgroup *groups, int n_groups,
+void launch_write(const sd_gather_grid &g, hipStream_t st, const sd_dev_model &dm, const double *psi, const sd_opgroup *groups, int n_groups,
                   const sd_opterm_dev *terms, const double *y, double br, double bi, double *out) {
   const dim3 grid(g.nb), blk(256);
-  if (g.mode == 1)
-    hipLaunchKernelGGL((k_opstring<NCI, NCO, 1, FUSED>), grid, blk, g.lbin_bytes, st, dm, psi, groups, n_groups, terms, y, br, bi, out);
-  else if (g.mode == 2)
-    hipLaunchKernelGGL((k_opstring<NCI, NCO, 2, FUSED>), grid, blk, g.lbin_bytes, st, dm, psi, groups, n_groups, terms, y, br, bi, out);
-  else
-    hipLaunchKernelGGL((k_opstring<NCI, NCO, 0, FUSED>), grid, blk, g.lbin_bytes, st, dm, psi, groups, n_groups, terms, y, br, bi, out);
+  sd_with_mode(g.mode, [&](auto M) {
+    hipLaunchKernelGGL((k_opstring<NCI, NCO, decltype(M)::value, FUSED>), grid, blk, g.lbin_bytes, st, dm, psi, groups, n_groups, terms, y,
+                       br, bi, out);
+  });
 }
 
 template <int NC>
-void launch_expect(const OpsGrid &g, unsigned nchunks, hipStream_t st, const sd_dev_model &dm, const double *bra, const double *ket,
+void launch_expect(const sd_gather_grid &g, unsigned nchunks, hipStream_t st, const sd_dev_model &dm, const double *bra, const double *ket,
                    const sd_opgroup *groups, const int32_t *op_first, const sd_opterm_dev *terms, int n_ops, double *partials) {
   const dim3 grid(nchunks, g.nb), blk(256);
   const size_t shmem = 32 * sizeof(double) + g.lbin_bytes;
-  if (g.mode == 1)
-    hipLaunchKernelGGL((k_opstring_expect<NC, 1>), grid, blk, shmem, st, dm, bra, ket, groups, op_first, terms, n_ops, partials);
-  else if (g.mode == 2)
-    hipLaunchKernelGGL((k_opstring_expect<NC, 2>), grid, blk, shmem, st, dm, bra, ket, groups, op_first, terms, n_ops, partials);
-  else
-    hipLaunchKernelGGL((k_opstring_expect<NC, 0>), grid, blk, shmem, st, dm, bra, ket, groups, op_first, terms, n_ops, partials);
+  sd_with_mode(g.mode, [&](auto M) {
+    hipLaunchKernelGGL((k_opstring_expect<NC, decltype(M)::value>), grid, blk, shmem, st, dm, bra, ket, groups, op_first, terms, n_ops,
+                       partials);
+  });
 }
 
-int ops_common(sd_ctx *ctx, const sd_model *m, int dtype) {
-  if (!m->dev_ready) return sd_set_err(ctx, SD_EARG, "model has no device tables (created without a context)");
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "operator strings need an unsharded model");
-  if (m->L < 1 || m->L > SD_MAX_L) return sd_set_err(ctx, SD_EARG, "operator strings need 1 <= L <= 63");
-  return SD_OK;
+int ops_common(sd_ctx *ctx, const sd_model *m, int dtype) { return sd_gather_check(ctx, m, dtype, "operator strings need", true); }
+
+// every launcher here takes at least one block
+sd_gather_grid ops_grid(const sd_model *m, bool reduction) {
+  sd_gather_grid g = reduction ? sd_gather_grid_of(m, SD_OPS_RED_BLOCKS, SD_OPS_RED_BLOCKS)
+                               : sd_gather_grid_of(m, SD_OPS_TILE_BLOCKS, SD_OPS_ROW_BLOCKS);
+  g.nb = std::max(g.nb, 1u);
+  return g;
 }
 
 }  // namespace
@@ -221,7 +182,7 @@ int sd_launch_opstring(sd_ctx *ctx, const sd_model *m, int dtype, const void *ps
   if (dtype_out == SD_F64 && y && b_im != 0.0) return sd_set_err(ctx, SD_EARG, "a Float64 output takes a real b (b_im = 0)");
   const sd_dev_model &dm = m->dm;
   if (dm.n_local == 0) return SD_OK;
-  const OpsGrid g = ops_grid(m, false);
+  const sd_gather_grid g = ops_grid(m, false);
   const double *p = (const double *)psi, *yv = (const double *)y;
   double *o = (double *)out;
   hipStream_t st = ctx->stream;
@@ -249,7 +210,7 @@ int sd_launch_opstring_expect(sd_ctx *ctx, const sd_model *m, int dtype, const v
     SD_HIP(ctx, hipMemsetAsync(dst, 0, 2 * (size_t)n_ops * sizeof(double), ctx->stream));
     return SD_OK;
   }
-  const OpsGrid g = ops_grid(m, true);
+  const sd_gather_grid g = ops_grid(m, true);
   const unsigned nchunks = (unsigned)((n_ops + SD_OPS_CHUNK - 1) / SD_OPS_CHUNK);
   rc = sd_ensure_partials(ctx, 2 * (size_t)n_ops * g.nb);
   if (rc) return rc;

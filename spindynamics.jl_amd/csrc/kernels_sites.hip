@@ -127,6 +127,7 @@ __global__ __launch_bounds__(1024) void k_site_reduce(const double *__restrict__
 
 // Chunked form for plans without tiles (per-row rank / unrank, sd_model_path == 0) and for whatever the one-pass form does
 // not take: SD_SITE_CHUNK sites per pass over the two vectors, like k_obs.  Partial row of a block: 16 site doubles, |ket|^2, 0.
+// Not the shared row walk (for_rows, gather_common.hpp): dm.p at run time, a blockDim.x stride, dm.row_lo for sharded full bases.
 #define SD_SITE_CROW 32
 template <int NCB>
 __global__ __launch_bounds__(256) void k_site_chunk(sd_dev_model dm, const double *__restrict__ bra, int64_t bra_bstride,

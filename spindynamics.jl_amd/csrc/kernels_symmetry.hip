@@ -9,20 +9,20 @@
 //   k_sym_overlaps <bra|U_g|ket> = sum_s conj(bra[s]) ket[src_g(s)] for a list of elements in one pass.  Layout of k_pairs: workgroup
 //                  column blockIdx.x owns a chunk of SD_SYM_CHUNK elements, blockIdx.y a share of the rows, the chunk is the FAST grid
 //                  index so that the workgroups in flight read the same rows of bra; per-thread accumulators, block_reduce2, block
-//                  partials in ctx->d_partials, k_sym_reduce adds them in a fixed order.  No atomics, and the grid depends on the plan
+//                  partials in ctx->d_partials, k_chunk_reduce adds them in a fixed order.  No atomics, and the grid depends on the plan
 //                  alone: the same call gives the same bits.
 //   k_sym_project  out = sum_g c_g U_g psi for a list with complex coefficients in one pass: every row gathers once per element.
 //                  ORDER (the restatement tests/symmetry_ref.py follows it): (re, im) start at (0, 0); elements in list order; the
 //                  term of element g is t = c_g psi[src_g(s)] with t_re = c_re v_re - c_im v_im and t_im = c_re v_im + c_im v_re formed
 //                  first (for a Float64 psi t_re = c_re v, t_im = c_im v), then re += t_re, im += t_im.  Nothing is fused.
-// Row configurations (MODE), as k_pairs: 1 the tile's prefix and the suffix table of a tiled sector plan, 0 unrank_g of the row, 2 the
-// row index (full basis).  Source row of a configuration t (sym_row): MODE 1 the plan's own rank addr[prefix of t] +
-// suf_rank[suffix of t], two cached loads; MODE 0 rank_g with the binomials in LDS; MODE 2 t itself.
+// Rows and their configurations (MODE) by for_rows (gather_common.hpp): 1 the tile's prefix and the suffix table of a tiled sector
+// plan, 0 unrank_g of the row, 2 the row index (full basis).  Source row of a configuration t by config_row (same header): MODE 1 the
+// plan's own rank addr[prefix of t] + suf_rank[suffix of t], two cached loads; MODE 0 rank_g with the binomials in LDS; MODE 2 t itself.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "device_common.hpp"
+#include "gather_common.hpp"
 
 using namespace sd_dev;
 
@@ -42,44 +42,6 @@ __device__ __forceinline__ uint64_t sym_source(uint64_t s, int code, int L, uint
   return s;
 }
 
-// lbin[n * K + k] = C(n, k), n < L, k < K = nup + 1 (MODE 0)
-template <int MODE>
-__device__ __forceinline__ int64_t sym_row(const sd_dev_model &dm, const int64_t *lbin, int K, uint64_t t) {
-  if (MODE == 2) return (int64_t)t;
-  if (MODE == 1) return dm.addr[(uint32_t)t & (((uint32_t)1 << dm.p) - 1u)] + (int64_t)dm.suf_rank[t >> dm.p];
-  int64_t idx = 0;
-  int r = dm.nup;
-  for (int b = 0; b < dm.L && r > 0; ++b) {
-    if ((t >> b) & 1) --r;
-    else idx += lbin[(dm.L - 1 - b) * K + r - 1];
-  }
-  return idx;
-}
-
-__device__ __forceinline__ void sym_fill_lbin(const sd_dev_model &dm, int64_t *lbin, int K) {
-  for (int k = threadIdx.x; k < dm.L * K; k += 256) lbin[k] = dm.binom[(k / K) * (SD_MAX_L + 1) + (k % K)];
-  __syncthreads();
-}
-
-// row(s, idx) for this workgroup's share of the rows: workgroup `blk` of `nblk`
-template <int MODE, class F>
-__device__ __forceinline__ void sym_rows(const sd_dev_model &dm, unsigned blk, unsigned nblk, F &&row) {
-  if (MODE == 1) {
-    for (int t = blk; t < dm.n_tiles; t += nblk) {
-      const uint32_t P = dm.tile_prefix[t];
-      const int64_t base = dm.tile_base[t];
-      const int t2 = dm.nup - __popc(P);
-      const int len = (int)binom_g(dm, dm.LS, t2);
-      const uint16_t *__restrict__ sufS = dm.suf_states + dm.suf_off[t2];
-      for (int i = threadIdx.x; i < len; i += 256) row((uint64_t)P | ((uint64_t)sufS[i] << dm.p), base + i);
-    }
-  } else {
-    const int64_t stride = (int64_t)nblk * 256;
-    for (int64_t idx = (int64_t)blk * 256 + threadIdx.x; idx < dm.n_local; idx += stride)
-      row(MODE == 2 ? (uint64_t)idx : unrank_g(dm, idx), idx);
-  }
-}
-
 // out = U_g x (+ (cr + i ci) y, FUSED; a Float64 launch has ci == 0)
 template <int NC, int MODE, bool FUSED>
 __global__ __launch_bounds__(256) void k_sym_apply(sd_dev_model dm, int code, const double *__restrict__ x, const double *y,
@@ -87,10 +49,10 @@ __global__ __launch_bounds__(256) void k_sym_apply(sd_dev_model dm, int code, co
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int64_t *lbin = reinterpret_cast<int64_t *>(smem);
   const int K = (dm.nup > 0 ? dm.nup : 0) + 1;
-  if (MODE == 0) sym_fill_lbin(dm, lbin, K);
+  fill_lbin<MODE>(dm, lbin, K);
   const uint64_t mask = ~(uint64_t)0 >> (64 - dm.L);
-  sym_rows<MODE>(dm, blockIdx.x, gridDim.x, [&](uint64_t s, int64_t idx) {
-    const int64_t src = sym_row<MODE>(dm, lbin, K, sym_source(s, code, dm.L, mask));
+  for_rows<MODE>(dm, blockIdx.x, gridDim.x, [&](uint64_t s, int64_t idx) {
+    const int64_t src = config_row<MODE>(dm, lbin, K, sym_source(s, code, dm.L, mask));
     if (NC == 2) {
       double2 v = ((const double2 *)x)[src];
       if (FUSED) {
@@ -114,21 +76,21 @@ __global__ __launch_bounds__(256) void k_sym_overlaps(sd_dev_model dm, const dou
   double *red = reinterpret_cast<double *>(smem);            // 32 doubles
   int64_t *lbin = reinterpret_cast<int64_t *>(red + 32);
   const int K = (dm.nup > 0 ? dm.nup : 0) + 1;
-  if (MODE == 0) sym_fill_lbin(dm, lbin, K);
+  fill_lbin<MODE>(dm, lbin, K);
   const uint64_t mask = ~(uint64_t)0 >> (64 - dm.L);
   const int c0 = blockIdx.x * SD_SYM_CHUNK, cn = min(SD_SYM_CHUNK, ncodes - c0);
   int cd[SD_SYM_CHUNK];
   double ar[SD_SYM_CHUNK], ai[SD_SYM_CHUNK];
 #pragma unroll
   for (int k = 0; k < SD_SYM_CHUNK; ++k) { cd[k] = k < cn ? codes[c0 + k] : 0; ar[k] = 0.0; ai[k] = 0.0; }
-  sym_rows<MODE>(dm, blockIdx.y, gridDim.y, [&](uint64_t s, int64_t idx) {
+  for_rows<MODE>(dm, blockIdx.y, gridDim.y, [&](uint64_t s, int64_t idx) {
     double br, bi = 0.0;
     if (NC == 2) { const double2 b = ((const double2 *)bra)[idx]; br = b.x; bi = b.y; }
     else br = bra[idx];
 #pragma unroll
     for (int k = 0; k < SD_SYM_CHUNK; ++k) {
       if (k >= cn) continue;
-      const int64_t src = sym_row<MODE>(dm, lbin, K, sym_source(s, cd[k], dm.L, mask));
+      const int64_t src = config_row<MODE>(dm, lbin, K, sym_source(s, cd[k], dm.L, mask));
       if (NC == 2) {
         const double2 u = ((const double2 *)ket)[src];
         ar[k] += br * u.x + bi * u.y;                        // conj(bra[s]) * ket[src]
@@ -148,24 +110,6 @@ __global__ __launch_bounds__(256) void k_sym_overlaps(sd_dev_model dm, const dou
   }
 }
 
-// Block c sums the partial rows of chunk c in a fixed order (16 strided sums per column, then their sum), as k_pairs_reduce.
-__global__ __launch_bounds__(256) void k_sym_reduce(const double *__restrict__ partials, int nblocks, int ncodes,
-                                                    double *__restrict__ out) {
-  __shared__ double sm[16][SD_SYM_ROW];
-  const int c = threadIdx.x & (SD_SYM_ROW - 1), j = threadIdx.x >> 4;
-  const double *__restrict__ p = partials + (size_t)blockIdx.x * nblocks * SD_SYM_ROW;
-  double a = 0.0;
-  for (int b = j; b < nblocks; b += 16) a += p[(size_t)b * SD_SYM_ROW + c];
-  sm[j][c] = a;
-  __syncthreads();
-  if (threadIdx.x < SD_SYM_ROW) {
-    double t = 0.0;
-    for (int jj = 0; jj < 16; ++jj) t += sm[jj][c];
-    const int e = blockIdx.x * SD_SYM_CHUNK + (c >> 1);
-    if (e < ncodes) out[2 * (size_t)e + (c & 1)] = t;
-  }
-}
-
 // NCI / NCO: components of psi / out (NCO >= NCI; NCO == 1 only with every coefficient real).  coef[2g .. +1] = c_g.
 template <int NCI, int NCO, int MODE>
 __global__ __launch_bounds__(256) void k_sym_project(sd_dev_model dm, const double *__restrict__ psi, const int *__restrict__ codes,
@@ -173,13 +117,13 @@ __global__ __launch_bounds__(256) void k_sym_project(sd_dev_model dm, const doub
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int64_t *lbin = reinterpret_cast<int64_t *>(smem);
   const int K = (dm.nup > 0 ? dm.nup : 0) + 1;
-  if (MODE == 0) sym_fill_lbin(dm, lbin, K);
+  fill_lbin<MODE>(dm, lbin, K);
   const uint64_t mask = ~(uint64_t)0 >> (64 - dm.L);
-  sym_rows<MODE>(dm, blockIdx.x, gridDim.x, [&](uint64_t s, int64_t idx) {
+  for_rows<MODE>(dm, blockIdx.x, gridDim.x, [&](uint64_t s, int64_t idx) {
     double re = 0.0, im = 0.0;
     for (int g = 0; g < ncodes; ++g) {                       // list order: see ORDER at the top
       const double cr = coef[2 * g], ci = coef[2 * g + 1];
-      const int64_t src = sym_row<MODE>(dm, lbin, K, sym_source(s, codes[g], dm.L, mask));
+      const int64_t src = config_row<MODE>(dm, lbin, K, sym_source(s, codes[g], dm.L, mask));
       if (NCI == 2) {
         const double2 v = ((const double2 *)psi)[src];
         const double tr = cr * v.x - ci * v.y, ti = cr * v.y + ci * v.x;
@@ -195,52 +139,38 @@ __global__ __launch_bounds__(256) void k_sym_project(sd_dev_model dm, const doub
   });
 }
 
-struct SymGrid { int mode; unsigned nb; size_t lbin_bytes; };
-SymGrid sym_grid(const sd_model *m, bool reduction) {
-  const sd_dev_model &dm = m->dm;
-  SymGrid g;
-  g.mode = dm.nup < 0 ? 2 : (m->p >= 0 && dm.n_tiles > 0) ? 1 : 0;
-  const int64_t nb64 = g.mode == 1 ? (int64_t)dm.n_tiles : (dm.n_local + 255) / 256;
-  const int64_t cap = reduction ? SD_SYM_RED_BLOCKS : g.mode == 1 ? SD_SYM_TILE_BLOCKS : SD_SYM_ROW_BLOCKS;
-  g.nb = (unsigned)std::min<int64_t>(nb64, cap);
-  g.lbin_bytes = g.mode == 0 ? (size_t)dm.L * (size_t)(dm.nup + 1) * sizeof(int64_t) : 0;
-  return g;
-}
-
 template <int NC, bool FUSED>
-void launch_apply(const SymGrid &g, hipStream_t st, const sd_dev_model &dm, int code, const double *x, const double *y, double cr,
+void launch_apply(const sd_gather_grid &g, hipStream_t st, const sd_dev_model &dm, int code, const double *x, const double *y, double cr,
                   double ci, double *out) {
   const dim3 grid(g.nb), blk(256);
-  if (g.mode == 1) hipLaunchKernelGGL((k_sym_apply<NC, 1, FUSED>), grid, blk, g.lbin_bytes, st, dm, code, x, y, cr, ci, out);
-  else if (g.mode == 2) hipLaunchKernelGGL((k_sym_apply<NC, 2, FUSED>), grid, blk, g.lbin_bytes, st, dm, code, x, y, cr, ci, out);
-  else hipLaunchKernelGGL((k_sym_apply<NC, 0, FUSED>), grid, blk, g.lbin_bytes, st, dm, code, x, y, cr, ci, out);
+  sd_with_mode(g.mode, [&](auto M) {
+    hipLaunchKernelGGL((k_sym_apply<NC, decltype(M)::value, FUSED>), grid, blk, g.lbin_bytes, st, dm, code, x, y, cr, ci, out);
+  });
 }
 
 template <int NC>
-void launch_overlaps(const SymGrid &g, unsigned nchunks, hipStream_t st, const sd_dev_model &dm, const double *bra, const double *ket,
+void launch_overlaps(const sd_gather_grid &g, unsigned nchunks, hipStream_t st, const sd_dev_model &dm, const double *bra, const double *ket,
                      const int *codes, int ncodes, double *partials) {
   const dim3 grid(nchunks, g.nb), blk(256);
   const size_t shmem = 32 * sizeof(double) + g.lbin_bytes;
-  if (g.mode == 1) hipLaunchKernelGGL((k_sym_overlaps<NC, 1>), grid, blk, shmem, st, dm, bra, ket, codes, ncodes, partials);
-  else if (g.mode == 2) hipLaunchKernelGGL((k_sym_overlaps<NC, 2>), grid, blk, shmem, st, dm, bra, ket, codes, ncodes, partials);
-  else hipLaunchKernelGGL((k_sym_overlaps<NC, 0>), grid, blk, shmem, st, dm, bra, ket, codes, ncodes, partials);
+  sd_with_mode(g.mode, [&](auto M) {
+    hipLaunchKernelGGL((k_sym_overlaps<NC, decltype(M)::value>), grid, blk, shmem, st, dm, bra, ket, codes, ncodes, partials);
+  });
 }
 
 template <int NCI, int NCO>
-void launch_project(const SymGrid &g, hipStream_t st, const sd_dev_model &dm, const double *psi, const int *codes, const double *coef,
+void launch_project(const sd_gather_grid &g, hipStream_t st, const sd_dev_model &dm, const double *psi, const int *codes, const double *coef,
                     int ncodes, double *out) {
   const dim3 grid(g.nb), blk(256);
-  if (g.mode == 1) hipLaunchKernelGGL((k_sym_project<NCI, NCO, 1>), grid, blk, g.lbin_bytes, st, dm, psi, codes, coef, ncodes, out);
-  else if (g.mode == 2) hipLaunchKernelGGL((k_sym_project<NCI, NCO, 2>), grid, blk, g.lbin_bytes, st, dm, psi, codes, coef, ncodes, out);
-  else hipLaunchKernelGGL((k_sym_project<NCI, NCO, 0>), grid, blk, g.lbin_bytes, st, dm, psi, codes, coef, ncodes, out);
+  sd_with_mode(g.mode, [&](auto M) {
+    hipLaunchKernelGGL((k_sym_project<NCI, NCO, decltype(M)::value>), grid, blk, g.lbin_bytes, st, dm, psi, codes, coef, ncodes, out);
+  });
 }
 
-int sym_common(sd_ctx *ctx, const sd_model *m, int dtype) {
-  if (!m->dev_ready) return sd_set_err(ctx, SD_EARG, "model has no device tables (created without a context)");
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "symmetry operators need an unsharded model");
-  if (m->L < 1 || m->L > SD_MAX_L) return sd_set_err(ctx, SD_EARG, "symmetry operators need 1 <= L <= 63");
-  return SD_OK;
+int sym_common(sd_ctx *ctx, const sd_model *m, int dtype) { return sd_gather_check(ctx, m, dtype, "symmetry operators need", true); }
+
+sd_gather_grid sym_grid(const sd_model *m, bool reduction) {
+  return reduction ? sd_gather_grid_of(m, SD_SYM_RED_BLOCKS, SD_SYM_RED_BLOCKS) : sd_gather_grid_of(m, SD_SYM_TILE_BLOCKS, SD_SYM_ROW_BLOCKS);
 }
 
 }  // namespace
@@ -253,7 +183,7 @@ int sd_launch_symmetry_apply(sd_ctx *ctx, const sd_model *m, int dtype, int code
   if (dtype == SD_F64 && y && ci != 0.0) return sd_set_err(ctx, SD_EARG, "a Float64 vector takes a real coefficient");
   const sd_dev_model &dm = m->dm;
   if (dm.n_local == 0) return SD_OK;
-  const SymGrid g = sym_grid(m, false);
+  const sd_gather_grid g = sym_grid(m, false);
   const double *xv = (const double *)x, *yv = (const double *)y;
   double *o = (double *)out;
   if (dtype == SD_C128) {
@@ -277,13 +207,13 @@ int sd_launch_symmetry_overlaps(sd_ctx *ctx, const sd_model *m, int dtype, const
     SD_HIP(ctx, hipMemsetAsync(dst, 0, 2 * (size_t)ncodes * sizeof(double), ctx->stream));
     return SD_OK;
   }
-  const SymGrid g = sym_grid(m, true);
+  const sd_gather_grid g = sym_grid(m, true);
   const unsigned nchunks = (unsigned)((ncodes + SD_SYM_CHUNK - 1) / SD_SYM_CHUNK);
   rc = sd_ensure_partials(ctx, (size_t)nchunks * g.nb * SD_SYM_ROW);
   if (rc) return rc;
   if (dtype == SD_C128) launch_overlaps<2>(g, nchunks, ctx->stream, dm, (const double *)bra, (const double *)ket, codes_dev, ncodes, ctx->d_partials);
   else launch_overlaps<1>(g, nchunks, ctx->stream, dm, (const double *)bra, (const double *)ket, codes_dev, ncodes, ctx->d_partials);
-  hipLaunchKernelGGL(k_sym_reduce, dim3(nchunks), dim3(256), 0, ctx->stream, ctx->d_partials, (int)g.nb, ncodes, dst);
+  hipLaunchKernelGGL(k_chunk_reduce<SD_SYM_CHUNK>, dim3(nchunks), dim3(256), 0, ctx->stream, ctx->d_partials, (int)g.nb, ncodes, 1.0, dst);
   SD_HIP(ctx, hipGetLastError());
   return SD_OK;
 }
@@ -297,7 +227,7 @@ int sd_launch_symmetry_project(sd_ctx *ctx, const sd_model *m, int dtype_in, con
   if (ncodes < 1 || ncodes > SD_SYM_MAX_ELEMENTS) return sd_set_err(ctx, SD_EINTERNAL, "symmetry projector: bad element count");
   const sd_dev_model &dm = m->dm;
   if (dm.n_local == 0) return SD_OK;
-  const SymGrid g = sym_grid(m, false);
+  const sd_gather_grid g = sym_grid(m, false);
   const double *p = (const double *)psi;
   double *o = (double *)out;
   if (dtype_in == SD_C128) launch_project<2, 2>(g, ctx->stream, dm, p, codes_dev, coef_dev, ncodes, o);
