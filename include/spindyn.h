@@ -806,8 +806,18 @@ int sd_symtridiag_eig(int n, const double *d, const double *e, double *w, double
  * eigenvalues w[n], eigenvectors in the columns of Z (n*n column-major).  The projected matrix of a restarted Lanczos basis is
  * arrowhead plus tridiagonal, which sd_symtridiag_eig cannot take.  SD_EARG: n outside 1..128 or a NULL pointer. */
 int sd_sym_eig(int n, const double *A, double *w, double *Z);
-/* Chebyshev expansion coefficients c_k (src/TimeEvolution/Chebyshev.jl:74-79); c_out has 2*cheb_n doubles */
+/* Chebyshev expansion coefficients c_k = (2 - delta_k0) (-i)^k J_k(a dt) exp(-i b dt), k < cheb_n (src/TimeEvolution/Chebyshev.jl:
+ * 74-79); c_out has 2*cheb_n doubles (re, im).  The contract every real-time Chebyshev entry point inherits:
+ *   accuracy  J_k is the Bessel function of the Float64 product a * dt, all orders from one backward recurrence in extended
+ *             precision, rounded once: |c_k - exact| <= 4 * 2^-53 at b = 0, <= 8 * 2^-53 with the phase (cos, sin of the Float64
+ *             product b * dt), at every |a dt| <= 1e6 and every k.  The call is O(|a dt| + cheb_n).
+ *   sign      dt < 0 evolves backwards: J_k(-z) = (-1)^k J_k(z), and c(-dt) is the complex conjugate of c(dt) bit for bit.
+ *   cap       SD_EARG for |a dt| > 1e6, a, b or dt not finite, cheb_n < 1 or c_out NULL; nothing else fails but allocation.
+ * sd_chebyshev_terms: *n_terms = the first k with k > |z| and |J_k(z)| < 2^-53 -- the term count that cheb_n = 0 stands for in
+ * sd_dqt_correlations, exact at every |z| <= 1e6 (the rule is read off the same recurrence, with no search cap); SD_EARG for
+ * |z| > 1e6, a NaN or n_terms NULL. */
 int sd_chebyshev_coeffs(int cheb_n, double a, double b, double dt, double *c_out);
+int sd_chebyshev_terms(double z, int *n_terms);
 /* counter-based N(0,1) generator used for synthetic vectors: element k of the
  * stream (seed) -- identical on host and device, independent of sharding. */
 int sd_fill_randn_dev(sd_ctx *ctx, void *x_dev, int64_t n_doubles, uint64_t seed, uint64_t first_index);

@@ -21,7 +21,7 @@ using Libdl
 export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_vector, create_spin_operator,
        groundstate, lowest_eigenpairs, time_evolve, structure_factor, dynamical_structure_factor,
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
-       chebyshev_imag_coeffs, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, CutBlock, cut_blocks, cut_gram, permute_sites, site_permute_sources, subsystem_permutation, subsystem_gram, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
+       chebyshev_imag_coeffs, chebyshev_terms, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, CutBlock, cut_blocks, cut_gram, permute_sites, site_permute_sources, subsystem_permutation, subsystem_gram, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
        DiagonalDrive, field_drive, gradient_drive, zz_drive, drive_check, diagonal_apply, driven_apply, magnus_schedule, piecewise_schedule, stage_evolve, driven_time_evolve,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
@@ -499,6 +499,13 @@ function chebyshev_imag_coeffs(a::Real, τ::Real; n_max::Int=4096)
     check(ccall((:sd_chebyshev_imag_coeffs, libspindyn), Cint, (Cint, Float64, Float64, Ptr{Float64}, Ref{Cint}),
                 n_max, Float64(a), Float64(τ), c, n_used))
     return c[1:n_used[]]
+end
+
+# the automatic real-time term count: the first k with k > |z| and |J_k(z)| < 2^-53, z = a Δt (|z| <= 1e6)
+function chebyshev_terms(z::Real)
+    n = Ref{Cint}(0)
+    check(ccall((:sd_chebyshev_terms, libspindyn), Cint, (Float64, Ref{Cint}), Float64(z), n))
+    return Int(n[])
 end
 
 # (exp(-βH/2) r / |.|, ln |exp(-βH/2) r|)

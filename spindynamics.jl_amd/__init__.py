@@ -11,7 +11,7 @@ from ._lib import (ArgumentError, Context, check, DimensionMismatch, SpinDynErro
 from .model import Model, XXZChain, build_model, long_range_hopping, momenta, nn_hopping
 from .hamiltonian import (Sminus_q_vector, Splus_q_vector, Sz_q_vector, apply_H, apply_rescaled_H, bit_at, cheb_step,
                           create_spin_operator, flip_bits, sz_value)
-from .solvers import (chebyshev_coeffs, chebyshev_time_evolve, compute_chebyshev_moments, estimate_energy_bounds,
+from .solvers import (chebyshev_coeffs, chebyshev_terms, chebyshev_time_evolve, compute_chebyshev_moments, estimate_energy_bounds,
                       get_kernel, get_rescaling_params, kpm_reconstruct, kpm_sqw, kpm_sqw_transverse, kpm_sw,
                       krylov_time_evolve, lanczos_extremal, lanczos_groundstate, lanczos_sqw, lanczos_sqw_transverse,
                       lanczos_tridiag, rescaling_from_bounds, spectral_from_tridiagonal, symtridiag_eig,

@@ -234,6 +234,7 @@ PROTOTYPES = {
     "sd_symtridiag_eig": (_i, [_i, _dp, _dp, _dp, _dp]),
     "sd_sym_eig": (_i, [_i, _dp, _dp, _dp]),
     "sd_chebyshev_coeffs": (_i, [_i, _d, _d, _d, _dp]),
+    "sd_chebyshev_terms": (_i, [_d, _ip]),
     "sd_fill_randn_dev": (_i, [_vp, _vp, _i64, _u64, _u64]),
     "sd_fill_randn_host": (_i, [_dp, _i64, _u64, _u64]),
     "sd_model_set_shard": (_i, [_vp, _i, _i]),

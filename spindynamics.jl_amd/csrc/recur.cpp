@@ -525,24 +525,89 @@ extern "C" int sd_symtridiag_eig(int n, const double *d_in, const double *e_in, 
   return SD_OK;
 }
 
-// c_k = (2 - delta_k0) * (-i)^k * J_k(a dt) * exp(-i b dt)   (src/TimeEvolution/Chebyshev.jl:74-79)
+namespace {
+
+// One real-time Chebyshev step takes |a dt| up to this: a million terms, a million applies.
+constexpr double SD_CHEB_ZMAX = 1e6;
+
+// J[k] = J_k(z) for k = 0 .. ktop, 0 <= z <= SD_CHEB_ZMAX, all orders from ONE backward recurrence (Miller):
+// f_{k-1} = (2k/z) f_k - f_{k+1} from f_{ktop+1} = 0, f_ktop = 1, normalised by the sum rule J_0 + 2 sum_{k>=1} J_2k = 1.  For
+// k > z, J_k is the recurrence's minimal solution and the downward direction damps every error; for k < z it is neutrally
+// stable, J and Y of one size, so that roundings add up at most linearly: 1e6 steps of 2^-64 stay below 1e-13 of the amplitude
+// sqrt(2/(pi z)) ~ 8e-4 there, far under an ulp of 1.  The start ktop = z + 64 + 24 z^(1/3) is 30 Airy widths (z/2)^(1/3) past the
+// turning point k = z, where J_k(z) ~ Ai((2/z)^(1/3) (k - z)) (2/z)^(1/3) < e^-100 J_z (64 orders do the same for z < 1); the
+// start's error is that ratio squared.  Orders above ktop are below 1e-100 and are given as zero.  The values grow by that
+// ratio on the way down and are rescaled before they can overflow (z << 1, where the ratio per step is 2k/z).  Extended
+// precision on the host, as scaled_bessel_i: the rounded values are the Bessel functions to an ulp of 1.
+// std::cyl_bessel_j cannot serve: libstdc++ switches to a Hankel form above z = 1000 that is invalid for k ~ z (overflow, NaN),
+// loses three digits below, throws for z < 0, and costs O(k) per order.
+void bessel_j_all(double z, std::vector<long double> &J) {
+  if (z == 0.0) { J.assign(1, 1.0L); return; }
+  const int ktop = (int)std::ceil(z) + 64 + (int)std::ceil(24.0 * std::cbrt(z));
+  const long double zl = (long double)z;
+  J.assign((size_t)ktop + 2, 0.0L);
+  J[ktop] = 1.0L;
+  for (int k = ktop; k >= 1; --k) {
+    const long double f = (long double)(2 * k) / zl * J[k] - J[k + 1];
+    J[k - 1] = f;
+    if (std::fabs(f) > 0x1p+8000L)
+      for (int j = k - 1; j <= ktop; ++j) J[j] *= 0x1p-8000L;
+  }
+  long double S = 0.0L;
+  for (int k = ktop - (ktop & 1); k >= 2; k -= 2) S += J[k];
+  S = 2.0L * S + J[0];
+  J.resize((size_t)ktop + 1);
+  for (long double &x : J) x /= S;
+}
+
+// real-time term count: the first k with k > z and |J_k(z)| < 2^-53, z = |a dt| <= SD_CHEB_ZMAX.  Read off the recurrence's own
+// values, which reach 14 Airy widths past the point where the rule is met (at z = 1e5 that is k = 100479, at 1e6 1001015),
+// so the search needs no cap.
+int cheb_auto_terms(double z) {
+  std::vector<long double> J;
+  bessel_j_all(z, J);
+  int k = (int)std::floor(z) + 1;
+  while (k < (int)J.size() && !(std::fabs(J[k]) < 0x1p-53L)) ++k;
+  return k;
+}
+
+}  // namespace
+
+// c_k = (2 - delta_k0) * (-i)^k * J_k(a dt) * exp(-i b dt)   (src/TimeEvolution/Chebyshev.jl:74-79), k = 0 .. cheb_n - 1.
+// J_k(a dt) is the Bessel function of the Float64 product a * dt rounded once from extended precision (bessel_j_all), for
+// |a dt| <= 1e6 at any cheb_n; a dt < 0 (backward in time) through J_k(-z) = (-1)^k J_k(z), which makes c(-dt) the conjugate of
+// c(dt) bit for bit.  cos and sin of the Float64 product b * dt.  SD_EARG: cheb_n < 1, c NULL, a, b or dt not finite, |a dt| > 1e6.
 extern "C" int sd_chebyshev_coeffs(int cheb_n, double a, double b, double dt, double *c) {
   if (cheb_n < 1 || !c) return SD_EARG;
-  const double ph = b * dt, pr = std::cos(ph), pi = -std::sin(ph);
-  for (int k = 0; k < cheb_n; ++k) {
-    const double f = (k == 0) ? 1.0 : 2.0;
-    const double J = std::cyl_bessel_j((double)k, a * dt);   // besselj(k, x), integer order
-    double xr, xi;
-    switch (k & 3) {
-      case 0: xr = f; xi = 0; break;
-      case 1: xr = 0; xi = -f; break;
-      case 2: xr = -f; xi = 0; break;
-      default: xr = 0; xi = f; break;
+  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(dt)) return SD_EARG;
+  const double z = a * dt;
+  if (!(std::fabs(z) <= SD_CHEB_ZMAX)) return SD_EARG;
+  try {
+    std::vector<long double> Jz;
+    bessel_j_all(std::fabs(z), Jz);
+    const double ph = b * dt, pr = std::cos(ph), pi = -std::sin(ph);
+    for (int k = 0; k < cheb_n; ++k) {
+      const double f = (k == 0) ? 1.0 : 2.0;
+      double J = (size_t)k < Jz.size() ? (double)Jz[k] : 0.0;
+      if (z < 0.0 && (k & 1)) J = -J;
+      double xr, xi;
+      switch (k & 3) {
+        case 0: xr = f; xi = 0; break;
+        case 1: xr = 0; xi = -f; break;
+        case 2: xr = -f; xi = 0; break;
+        default: xr = 0; xi = f; break;
+      }
+      xr *= J; xi *= J;
+      c[2 * k] = xr * pr - xi * pi;
+      c[2 * k + 1] = xr * pi + xi * pr;
     }
-    xr *= J; xi *= J;
-    c[2 * k] = xr * pr - xi * pi;
-    c[2 * k + 1] = xr * pi + xi * pr;
-  }
+  } catch (...) { return SD_ENOMEM; }
+  return SD_OK;
+}
+
+extern "C" int sd_chebyshev_terms(double z, int *n_terms) {
+  if (!n_terms || !(std::fabs(z) <= SD_CHEB_ZMAX)) return SD_EARG;
+  try { *n_terms = cheb_auto_terms(std::fabs(z)); } catch (...) { return SD_ENOMEM; }
   return SD_OK;
 }
 
@@ -1043,8 +1108,10 @@ static int chebyshev_evolve_core(Op &op, const void *psi0, bool host_in, int64_t
   if (n != op.n) return sd_set_err(ctx, SD_EDIM, "vector length does not match the (local) basis dimension");
   if (cheb_n < 1) return sd_set_err(ctx, SD_EARG, "cheb_n must be >= 1");               // :65
   const double a = (Emax - Emin) / (2 * 0.9999), b = (Emax + Emin) / 2;                   // :70-71
+  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(dt)) return sd_set_err(ctx, SD_EARG, "the time step and the energy bounds must be finite");
+  if (!(std::fabs(a * dt) <= SD_CHEB_ZMAX)) return sd_set_err(ctx, SD_EARG, "a * dt is too large for one Chebyshev step (above 1e6): take several steps");
   std::vector<double> c(2 * (size_t)cheb_n);
-  sd_chebyshev_coeffs(cheb_n, a, b, dt, c.data());
+  RC(sd_chebyshev_coeffs(cheb_n, a, b, dt, c.data()));                                    // dt < 0 evolves backwards, as the reference's besselj does
   DBuf b0, b1, b2, ptb;
   RC(b0.alloc(ctx, 2 * n)); RC(b1.alloc(ctx, 2 * n)); RC(b2.alloc(ctx, 2 * n));
   double *pprev = b0.p, *pcur = b1.p, *pnext = b2.p;
@@ -1682,16 +1749,6 @@ void scaled_bessel_i(double z, std::vector<double> &e, int *n_used) {
   e.resize(nu);
   for (int k = 0; k < nu; ++k) e[k] = (double)(t[k] / S);
   *n_used = nu;
-}
-
-// real-time term count: the first k with k > z and |J_k(z)| < 2^-53, z = a dt
-// (the caller has checked 0 <= z <= SD_CHEB_ZMAX; the search is capped at k = z + 64 + 8 z^(1/3), well inside the Airy tail of J_k(z))
-constexpr double SD_CHEB_ZMAX = 1e6;
-int cheb_auto_terms(double z) {
-  int k = (int)std::floor(z) + 1;
-  const int kmax = (int)(z + 64.0 + 8.0 * std::cbrt(z));
-  while (k < kmax && !(std::fabs(std::cyl_bessel_j((double)k, z)) < 0x1p-53)) ++k;
-  return std::max(k, 1);
 }
 
 // Emin, Emax as given, or (Emax <= Emin) estimated as estimate_energy_bounds does; a spectrum of one point (a one-state sector)
@@ -2562,7 +2619,7 @@ extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, 
         if (!(a * dt <= SD_CHEB_ZMAX)) return sd_set_err(ctx, SD_EARG, "a * dt is too large for one Chebyshev step (above 1e6): give more time points");
         nterm = cheb_n > 0 ? cheb_n : cheb_auto_terms(a * dt);
         c.resize(2 * (size_t)nterm);
-        sd_chebyshev_coeffs(nterm, a, b, dt, c.data());
+        RC(sd_chebyshev_coeffs(nterm, a, b, dt, c.data()));
         c_dt = dt;
       }
       if (batched) {

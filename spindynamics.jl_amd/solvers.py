@@ -171,6 +171,14 @@ def chebyshev_coeffs(cheb_n, a, b, dt):
     return c
 
 
+def chebyshev_terms(z):
+    """The automatic real-time term count: the first k with k > |z| and |J_k(z)| < 2^-53, z = a dt (sd_chebyshev_terms).
+    ArgumentError for |z| > 1e6."""
+    n = C.c_int(0)
+    check(lib().sd_chebyshev_terms(float(z), C.byref(n)))
+    return n.value
+
+
 def rescaling_from_bounds(Emin, Emax):
     """_rescaling_from_bounds -- src/KPM_Sqw.jl:13-17"""
     a, b = C.c_double(), C.c_double()
