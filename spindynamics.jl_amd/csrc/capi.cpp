@@ -11,7 +11,7 @@
 #include <utility>
 #include <vector>
 
-#include "sd_internal.hpp"
+#include "host_calls.hpp"
 #include "site_perm.hpp"
 
 int sd_set_err(sd_ctx *ctx, int code, const std::string &msg) {
@@ -707,9 +707,8 @@ static int obs_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, i
   const int L = m->L;
   if (what == 0) return sd_launch_observable(ctx, m, dtype, psi, 0, out);       // magnetization_per_site
   std::vector<double> S(L), R(L), Cr(L);
-  int rc = sd_launch_observable(ctx, m, dtype, psi, 0, S.data());
-  if (!rc) rc = sd_launch_observable(ctx, m, dtype, psi, 1, R.data());
-  if (rc) return rc;
+  RC(sd_launch_observable(ctx, m, dtype, psi, 0, S.data()));
+  RC(sd_launch_observable(ctx, m, dtype, psi, 1, R.data()));
   for (int r = 0; r < L; ++r) {                                                   // src/Observables.jl:83-91
     double prod = 0.0;
     for (int i = 1; i <= L; ++i) { const int j = ((i + r - 1) % L) + 1; prod += S[i - 1] * S[j - 1]; }
@@ -733,29 +732,28 @@ static int obs_host(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, 
   if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
   const size_t bytes = (size_t)n * (dtype == SD_C128 ? 16 : 8);
   TmpDev d(ctx);
-  int rc = d.alloc(bytes);
-  if (rc) return rc;
-  if ((rc = sd_xfer_h2d(ctx, d.p, psi, bytes))) return rc;
+  RC(d.alloc(bytes));
+  RC(sd_xfer_h2d(ctx, d.p, psi, bytes));
   return obs_dev(ctx, m, dtype, d.p, n, what, out, q_out);
 }
 
 int sd_magnetization(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, double *mags_out) {
-  return obs_host(ctx, m, dtype, psi_host, n, 0, mags_out, nullptr);
+  return abi_guard(ctx, [&]() -> int { return obs_host(ctx, m, dtype, psi_host, n, 0, mags_out, nullptr); });
 }
 int sd_magnetization_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, double *mags_out) {
-  return obs_dev(ctx, m, dtype, psi_dev, n, 0, mags_out, nullptr);
+  return abi_guard(ctx, [&]() -> int { return obs_dev(ctx, m, dtype, psi_dev, n, 0, mags_out, nullptr); });
 }
 int sd_connected_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, double *C_out) {
-  return obs_host(ctx, m, dtype, psi_host, n, 1, C_out, nullptr);
+  return abi_guard(ctx, [&]() -> int { return obs_host(ctx, m, dtype, psi_host, n, 1, C_out, nullptr); });
 }
 int sd_connected_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, double *C_out) {
-  return obs_dev(ctx, m, dtype, psi_dev, n, 1, C_out, nullptr);
+  return abi_guard(ctx, [&]() -> int { return obs_dev(ctx, m, dtype, psi_dev, n, 1, C_out, nullptr); });
 }
 int sd_structure_factor(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, double *q_out, double *S_out) {
-  return obs_host(ctx, m, dtype, psi_host, n, 2, S_out, q_out);
+  return abi_guard(ctx, [&]() -> int { return obs_host(ctx, m, dtype, psi_host, n, 2, S_out, q_out); });
 }
 int sd_structure_factor_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, double *q_out, double *S_out) {
-  return obs_dev(ctx, m, dtype, psi_dev, n, 2, S_out, q_out);
+  return abi_guard(ctx, [&]() -> int { return obs_dev(ctx, m, dtype, psi_dev, n, 2, S_out, q_out); });
 }
 
 int sd_spin_operator(sd_ctx *ctx, const sd_model *m, int dtype, int site, int op, const void *psi_host, int64_t n,
@@ -845,26 +843,6 @@ int sd_fill_randn_host(double *x, int64_t n, uint64_t seed, uint64_t first) {
 
 // ---- entanglement across a chain cut (cut_plan.cpp, kernels_cut.hip) ----
 namespace {
-// no C++ exception may cross the C ABI: a failed host allocation of a plan comes back as a status
-template <class F>
-int cut_guard(sd_ctx *ctx, F &&body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc &) {
-    return sd_set_err(ctx, SD_ENOMEM, "out of host memory inside the call");
-  } catch (...) {
-    return sd_set_err(ctx, SD_EINTERNAL, "unexpected exception");
-  }
-}
-
-struct PoolTmp {   // a block of the context's pool, given back when the call returns
-  sd_ctx *ctx = nullptr;
-  void *p = nullptr;
-  size_t bytes = 0;
-  ~PoolTmp() { if (p) sd_pool_give(ctx, p, bytes); }
-  int take(sd_ctx *c, size_t want) { ctx = c; return sd_pool_take(c, want, &p, &bytes); }
-};
-
 int cut_gram_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int cut, int side, void *G_out, bool on_dev,
                   double *kernel_ms = nullptr) {
   if (!ctx) return SD_EARG;
@@ -873,23 +851,18 @@ int cut_gram_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, in
   if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
   sd_cut_plan plan;
   std::string err;
-  int rc = sd_cut_build_plan(m, cut, side, true, plan, err);
-  if (rc) return sd_set_err(ctx, rc, err);
+  if (int rc = sd_cut_build_plan(m, cut, side, true, plan, err)) return sd_set_err(ctx, rc, err);
   if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
   const size_t el = dtype == SD_C128 ? 16 : 8, out_bytes = (size_t)plan.n_out * el;
   if (kernel_ms) *kernel_ms = 0.0;
   if (m->N == 0) { if (G_out) memset(G_out, 0, out_bytes); return SD_OK; }
   SD_HIP(ctx, hipSetDevice(ctx->device));
-  PoolTmp in, res;
-  const void *p = psi;
-  if (!on_dev) {
-    if ((rc = in.take(ctx, (size_t)n * el))) return rc;
-    if ((rc = sd_xfer_h2d(ctx, in.p, psi, (size_t)n * el))) return rc;
-    p = in.p;
-  }
-  if ((rc = res.take(ctx, out_bytes))) return rc;
+  DevIn in;
+  DBuf res;
+  RC(in.stage(ctx, dtype, psi, on_dev, n));
+  RC(res.alloc_bytes(ctx, out_bytes));
   float ms = 0.0f;
-  if ((rc = sd_launch_cut_gram(ctx, m, dtype, p, plan, (double *)res.p, kernel_ms ? &ms : nullptr))) return rc;
+  RC(sd_launch_cut_gram(ctx, m, dtype, in.p, plan, res.p, kernel_ms ? &ms : nullptr));
   if (kernel_ms) *kernel_ms = ms;
   return G_out ? sd_xfer_d2h(ctx, G_out, res.p, out_bytes) : SD_OK;
 }
@@ -899,7 +872,7 @@ extern "C" {
 
 int sd_cut_blocks(const sd_model *m, int cut, int side, sd_cut_block *out, int cap, int *n_blocks, int64_t *n_elems) {
   if (!m || !n_blocks || !n_elems || cap < 0 || (cap > 0 && !out)) return SD_EARG;
-  return cut_guard(m->ctx, [&]() -> int {
+  return abi_guard(m->ctx, [&]() -> int {
     std::vector<sd_cut_blk> blks;
     std::string err;
     int64_t total = 0;
@@ -916,7 +889,7 @@ int sd_cut_blocks(const sd_model *m, int cut, int side, sd_cut_block *out, int c
 
 int sd_cut_plan_info(const sd_model *m, int cut, int side, int dtype, int64_t *n_items, int *max_ns, int64_t *workspace_bytes) {
   if (!m || !n_items || !max_ns || !workspace_bytes) return SD_EARG;
-  return cut_guard(m->ctx, [&]() -> int {
+  return abi_guard(m->ctx, [&]() -> int {
     if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(m->ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
     sd_cut_plan plan;
     std::string err;
@@ -931,7 +904,7 @@ int sd_cut_plan_info(const sd_model *m, int cut, int side, int dtype, int64_t *n
 
 int sd_cut_plan_items(const sd_model *m, int cut, int side, sd_cut_item *out, int64_t cap, int64_t *n_items) {
   if (!m || !n_items || cap < 0 || (cap > 0 && !out)) return SD_EARG;
-  return cut_guard(m->ctx, [&]() -> int {
+  return abi_guard(m->ctx, [&]() -> int {
     sd_cut_plan plan;
     std::string err;
     const int rc = sd_cut_build_plan(m, cut, side, false, plan, err);
@@ -946,7 +919,7 @@ int sd_cut_plan_items(const sd_model *m, int cut, int side, sd_cut_item *out, in
 
 int sd_cut_segments(const sd_model *m, int cut, int side, int block, int64_t *starts, int64_t cap, int64_t *n_seg, int64_t *seg_len) {
   if (!m || !n_seg || !seg_len || cap < 0 || (cap > 0 && !starts)) return SD_EARG;
-  return cut_guard(m->ctx, [&]() -> int {
+  return abi_guard(m->ctx, [&]() -> int {
     std::vector<sd_cut_blk> blks;
     std::string err;
     const int rc = sd_cut_layout(m, cut, side, blks, nullptr, err);
@@ -965,27 +938,22 @@ int sd_cut_segments(const sd_model *m, int cut, int side, int block, int64_t *st
 }
 
 int sd_cut_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int cut, int side, void *G_out) {
-  return cut_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_host, n, cut, side, G_out, false); });
+  return abi_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_host, n, cut, side, G_out, false); });
 }
 
 int sd_cut_gram_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int cut, int side, void *G_out) {
-  return cut_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_dev, n, cut, side, G_out, true); });
+  return abi_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_dev, n, cut, side, G_out, true); });
 }
 
 int sd_cut_gram_time_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int cut, int side, double *kernel_ms) {
   if (ctx && !kernel_ms) return sd_set_err(ctx, SD_EARG, "null argument");
-  return cut_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_dev, n, cut, side, nullptr, true, kernel_ms); });
+  return abi_guard(ctx, [&]() -> int { return cut_gram_core(ctx, m, dtype, psi_dev, n, cut, side, nullptr, true, kernel_ms); });
 }
 
 }  // extern "C"
 
 // ---- site permutations and the entanglement of any set of sites (site_perm.hpp, kernels_permute.hip) ----
 namespace {
-bool bytes_overlap(const void *a, const void *b, size_t n) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + n && y < x + n;
-}
-
 // what every vector call checks before anything is queued; pm receives the permutation
 int permute_args(sd_ctx *ctx, const sd_model *m, int dtype, const int *perm, sd_site_perm &pm, int *identity) {
   if (!m->dev_ready) return sd_set_err(ctx, SD_EARG, "model has no device tables (created without a context)");
@@ -999,19 +967,18 @@ int site_permute_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi
   if (!ctx) return SD_EARG;
   if (!m || !psi || !perm || !out) return sd_set_err(ctx, SD_EARG, "null argument");
   sd_site_perm pm;
-  int rc = permute_args(ctx, m, dtype, perm, pm, nullptr);
-  if (rc) return rc;
+  RC(permute_args(ctx, m, dtype, perm, pm, nullptr));
   if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
   const size_t bytes = (size_t)n * (dtype == SD_C128 ? 16 : 8);
-  if (bytes_overlap(out, psi, bytes)) return sd_set_err(ctx, SD_EARG, "out must not alias or overlap psi");
+  if (ranges_overlap(out, bytes, psi, bytes)) return sd_set_err(ctx, SD_EARG, "out must not alias or overlap psi");
   if (n == 0) return SD_OK;
   SD_HIP(ctx, hipSetDevice(ctx->device));
-  if (on_dev) return sd_launch_site_permute(ctx, m, dtype, pm, psi, out);
-  PoolTmp in, res;
-  if ((rc = in.take(ctx, bytes)) || (rc = res.take(ctx, bytes))) return rc;
-  if ((rc = sd_xfer_h2d(ctx, in.p, psi, bytes))) return rc;
-  if ((rc = sd_launch_site_permute(ctx, m, dtype, pm, in.p, res.p))) return rc;
-  return sd_xfer_d2h(ctx, out, res.p, bytes);
+  DevIn in;
+  DevOut o;
+  RC(in.stage(ctx, dtype, psi, on_dev, n));
+  RC(o.open(ctx, out, on_dev, vec_doubles(dtype, n)));
+  RC(sd_launch_site_permute(ctx, m, dtype, pm, in.p, o.p));
+  return o.close(false);                                   // the device form takes nothing from the pool
 }
 
 int subsystem_perm(int L, const int *sites, int n_sites, int *perm_out) {
@@ -1038,24 +1005,18 @@ int subsystem_gram_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *p
     return sd_set_err(ctx, SD_EARG, "the sites must be distinct, in 1..L, and 1 <= n_sites <= L - 1");
   sd_site_perm pm;
   int identity = 0;
-  int rc = permute_args(ctx, m, dtype, perm, pm, &identity);
-  if (rc) return rc;
+  RC(permute_args(ctx, m, dtype, perm, pm, &identity));
   std::vector<sd_cut_blk> blks;         // the cut's own refusals (side, block dimension) before anything is queued
   std::string err;
-  if ((rc = sd_cut_layout(m, n_sites, side, blks, nullptr, err))) return sd_set_err(ctx, rc, err);
+  if (int rc = sd_cut_layout(m, n_sites, side, blks, nullptr, err)) return sd_set_err(ctx, rc, err);
   if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
   if (identity || n == 0) return cut_gram_core(ctx, m, dtype, psi, n, n_sites, side, G_out, on_dev);
   SD_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = (size_t)n * (dtype == SD_C128 ? 16 : 8);
-  PoolTmp in, tmp;
-  const void *p = psi;
-  if (!on_dev) {
-    if ((rc = in.take(ctx, bytes))) return rc;
-    if ((rc = sd_xfer_h2d(ctx, in.p, psi, bytes))) return rc;
-    p = in.p;
-  }
-  if ((rc = tmp.take(ctx, bytes))) return rc;
-  if ((rc = sd_launch_site_permute(ctx, m, dtype, pm, p, tmp.p))) return rc;
+  DevIn in;
+  DBuf tmp;
+  RC(in.stage(ctx, dtype, psi, on_dev, n));
+  RC(tmp.alloc(ctx, vec_doubles(dtype, n)));
+  RC(sd_launch_site_permute(ctx, m, dtype, pm, in.p, tmp.p));
   return cut_gram_core(ctx, m, dtype, tmp.p, n, n_sites, side, G_out, true);   // returns after the stream has drained
 }
 }  // namespace
@@ -1063,18 +1024,18 @@ int subsystem_gram_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *p
 extern "C" {
 
 int sd_site_permute(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *perm, void *out_host) {
-  return cut_guard(ctx, [&]() -> int { return site_permute_core(ctx, m, dtype, psi_host, n, perm, out_host, false); });
+  return abi_guard(ctx, [&]() -> int { return site_permute_core(ctx, m, dtype, psi_host, n, perm, out_host, false); });
 }
 
 int sd_site_permute_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *perm, void *out_dev) {
-  return cut_guard(ctx, [&]() -> int { return site_permute_core(ctx, m, dtype, psi_dev, n, perm, out_dev, true); });
+  return abi_guard(ctx, [&]() -> int { return site_permute_core(ctx, m, dtype, psi_dev, n, perm, out_dev, true); });
 }
 
 int sd_site_permute_sources(const sd_model *m, const int *perm, int64_t start, int64_t count, int64_t *rows_out) {
   if (!m) return SD_EARG;
   if (!perm || start < 0 || count < 0 || start > m->N - count || (count > 0 && !rows_out))
     return sd_set_err(m->ctx, SD_EARG, "sd_site_permute_sources: null argument or rows outside the basis");
-  return cut_guard(m->ctx, [&]() -> int {
+  return abi_guard(m->ctx, [&]() -> int {
     sd_site_perm pm;
     if (!sd_site_perm_make(perm, m->L, &pm, nullptr)) return sd_set_err(m->ctx, SD_EARG, "perm must be a bijection of 1..L");
     const int ntab = (m->L + 7) / 8;
@@ -1090,12 +1051,12 @@ int sd_subsystem_permutation(int L, const int *sites, int n_sites, int *perm_out
 
 int sd_subsystem_gram(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *sites, int n_sites, int side,
                       void *G_out) {
-  return cut_guard(ctx, [&]() -> int { return subsystem_gram_core(ctx, m, dtype, psi_host, n, sites, n_sites, side, G_out, false); });
+  return abi_guard(ctx, [&]() -> int { return subsystem_gram_core(ctx, m, dtype, psi_host, n, sites, n_sites, side, G_out, false); });
 }
 
 int sd_subsystem_gram_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *sites, int n_sites, int side,
                           void *G_out) {
-  return cut_guard(ctx, [&]() -> int { return subsystem_gram_core(ctx, m, dtype, psi_dev, n, sites, n_sites, side, G_out, true); });
+  return abi_guard(ctx, [&]() -> int { return subsystem_gram_core(ctx, m, dtype, psi_dev, n, sites, n_sites, side, G_out, true); });
 }
 
 }  // extern "C"
@@ -1154,7 +1115,7 @@ int sd_drive_build(const sd_model *m, const sd_drive *drives, int K, const doubl
 
 extern "C" int sd_drive_check(const sd_model *m, const sd_drive *drives, int K) {
   if (!m) return SD_EARG;
-  return cut_guard(m->ctx, [&]() -> int {
+  return abi_guard(m->ctx, [&]() -> int {
     std::string err;
     sd_drive_table none;
     const int rc = sd_drive_build(m, drives, K, nullptr, none, err);

@@ -3,6 +3,11 @@
 // epilogue where the recursion allows it) plus a few BLAS-1 kernels; only the
 // scalars the host-side tridiagonal / Chebyshev algebra needs cross PCIe.
 //
+// In this file: what runs an operator loop -- Lanczos (extremal values, bounds, ground state, tridiagonal, eigenpairs), Krylov and
+// Chebyshev evolution in real and imaginary time, KPM moments, S(q,w) by KPM and by Lanczos with the transverse and site-resolved
+// forms, the typicality driver, driven evolution -- and `Op`, the operator they share.  The one-pass observables are in
+// observe.cpp; the guard, the pool buffer and the staging of the caller's vectors are in host_calls.hpp.
+//
 // Reference functions followed (file:line under the reference repository):
 //   lanczos_extremal        src/Lanczos.jl:27-84
 //   estimate_energy_bounds  src/Lanczos.jl:255-271
@@ -20,55 +25,9 @@
 #include <string>
 #include <vector>
 
-#include "sd_internal.hpp"
+#include "host_calls.hpp"
 
 namespace {
-
-#define RC(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
-// No C++ exception may cross the C ABI: a failed host allocation (std::vector of the m x m work, std::string of a message) inside a
-// recursion comes back as a status.  Every extern "C" entry point below is abi_guard(ctx, [&]() -> int { body }).
-template <class F>
-int abi_guard(sd_ctx *ctx, F &&body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc &) {
-    return ctx ? sd_set_err(ctx, SD_ENOMEM, "out of host memory inside the call") : SD_ENOMEM;
-  } catch (const std::exception &e) {
-    return ctx ? sd_set_err(ctx, SD_EINTERNAL, std::string("unexpected exception: ") + e.what()) : SD_EINTERNAL;
-  } catch (...) {
-    return ctx ? sd_set_err(ctx, SD_EINTERNAL, "unexpected exception") : SD_EINTERNAL;
-  }
-}
-
-struct DBuf {   // device work vector, taken from / returned to the context's pool
-  double *p = nullptr;
-  sd_ctx *owner = nullptr;
-  size_t bytes = 0;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() {
-    if (p) sd_pool_give(owner, p, bytes);
-    p = nullptr; bytes = 0;
-  }
-  int alloc(sd_ctx *ctx, int64_t doubles) {
-    release();
-    owner = ctx;
-    void *q = nullptr;
-    int rc = sd_pool_take(ctx, sizeof(double) * (size_t)std::max<int64_t>(doubles, 1), &q, &bytes);
-    p = (double *)q;
-    return rc;
-  }
-};
-
-// the caller's host vectors (src/PublicAPI.jl:50-88): staged through the context's pinned ring when large (xfer.cpp)
-int h2d(sd_ctx *ctx, double *d, const void *h, int64_t doubles) { return sd_xfer_h2d(ctx, d, h, sizeof(double) * (size_t)doubles); }
-int d2h(sd_ctx *ctx, void *h, const double *d, int64_t doubles) { return sd_xfer_d2h(ctx, h, d, sizeof(double) * (size_t)doubles); }
-int d2d(sd_ctx *ctx, double *dst, const double *src, int64_t doubles) {
-  SD_HIP(ctx, hipMemcpyAsync(dst, src, sizeof(double) * (size_t)doubles, hipMemcpyDeviceToDevice, ctx->stream));
-  return SD_OK;
-}
 
 // The caller's operator (sd_ctx_set_apply_callback; the reference's `applyH!` argument): out <- H psi by the callback on the
 // context's stream, then the recursion's fused step as one elementwise pass over out.
@@ -216,8 +175,7 @@ int lanczos_fused(Op &op, int Qb, double *u0, int mm, int form, int negate, doub
     { double *old = uprev; uprev = ucur; ucur = t; t = old; }
     if (j % SD_BREAK_PEEK == 0 && j < mm - 1) {                          // stop queueing once EVERY vector has broken down
       peek.resize((size_t)(srow * Qb));
-      SD_HIP(ctx, hipMemcpyAsync(peek.data(), ab.p, sizeof(double) * peek.size(), hipMemcpyDeviceToHost, ctx->stream));
-      SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      RC(read_back(ctx, peek.data(), ab.p, sizeof(double) * peek.size()));
       bool all_broke = true;
       for (int q = 0; q < Qb && all_broke; ++q) {
         bool broke = false;
@@ -228,8 +186,7 @@ int lanczos_fused(Op &op, int Qb, double *u0, int mm, int form, int negate, doub
     }
   }
   std::vector<double> host((size_t)(srow * Qb));
-  SD_HIP(ctx, hipMemcpyAsync(host.data(), ab.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  RC(read_back(ctx, host.data(), ab.p, sizeof(double) * host.size()));
   alpha.assign((size_t)Qb * mm, 0.0); beta.assign((size_t)Qb * mm, 0.0);
   for (int q = 0; q < Qb; ++q)
     for (int k = 0; k < mm; ++k) { alpha[(size_t)q * mm + k] = host[(size_t)(srow * q) + k]; beta[(size_t)q * mm + k] = host[(size_t)(srow * q) + mm + k]; }
@@ -278,8 +235,7 @@ int lanczos_coeffs(Op &op, double *u0, int mm, int form, int negate, double tol,
     }
   }
   std::vector<double> host(2 * (size_t)mm);
-  SD_HIP(ctx, hipMemcpyAsync(host.data(), ab.p, sizeof(double) * 2 * (size_t)mm, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  RC(read_back(ctx, host.data(), ab.p, sizeof(double) * 2 * (size_t)mm));
   al.assign(host.begin(), host.begin() + mm); be.assign(host.begin() + mm, host.end());
   return SD_OK;
 }
@@ -372,8 +328,7 @@ int moments_dev(Op &op, const double *phi, int M, double a, double b, double *mu
       double *t = v_prev; v_prev = v_curr; v_curr = v_next; v_next = t;
     }
     std::vector<double> hs(2 * (size_t)nsteps);
-    SD_HIP(ctx, hipMemcpyAsync(hs.data(), sm.p, sizeof(double) * 2 * (size_t)nsteps, hipMemcpyDeviceToHost, ctx->stream));
-    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RC(read_back(ctx, hs.data(), sm.p, sizeof(double) * 2 * (size_t)nsteps));
     bool guard = false;
     for (int k = 1; k <= nsteps; ++k) {                         // sums of step k: [Re<v_{k-1}|v_k>, |v_k|^2]
       const double s0 = hs[2 * (size_t)(k - 1)], s1 = hs[2 * (size_t)(k - 1) + 1];
@@ -421,8 +376,7 @@ int moments_dev_batched(Op &op, const double *phi, int Qb, int M, double a, doub
     double *t = v_prev; v_prev = v_curr; v_curr = v_next; v_next = t;                               // :124
   }
   std::vector<double> hs((size_t)Qb * (size_t)srow);
-  SD_HIP(ctx, hipMemcpyAsync(hs.data(), sm.p, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  RC(read_back(ctx, hs.data(), sm.p, sizeof(double) * hs.size()));
   for (int q = 0; q < Qb; ++q) {
     const double *h = hs.data() + (size_t)q * (size_t)srow;
     double *m = mu + (size_t)q * (size_t)M;
@@ -843,9 +797,8 @@ extern "C" int sd_lanczos_groundstate(sd_ctx *ctx, const sd_model *m, int lanc_m
       if (j < mm) RC(sd_k_gs_scale(ctx, V.p + N * (int64_t)j, t, N, n2list(j), d_be + (j - 1)));   // :133, :155
       if (j >= 2) {
         // the step before: beta_{j-1} (breakdown, :136-139) and its orthogonality check (:142-153)
-        SD_HIP(ctx, hipMemcpyAsync(hb.data(), d_be + (j - 2), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         if (chk_now) SD_HIP(ctx, hipMemcpyAsync(hchk.data(), chkd.p, sizeof(double) * (size_t)(j - 1), hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RC(read_back(ctx, hb.data(), d_be + (j - 2), sizeof(double)));
         if (deferred) beta[j - 2] = hb[0];
         if (!(beta[j - 2] >= tol)) { m_actual = j - 1; break; }                            // (NaN counts as a breakdown)
         bool fired = false;
@@ -869,8 +822,7 @@ extern "C" int sd_lanczos_groundstate(sd_ctx *ctx, const sd_model *m, int lanc_m
       ++j;
     }
     std::vector<double> host(2 * (size_t)mm);
-    SD_HIP(ctx, hipMemcpyAsync(host.data(), ab.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost, ctx->stream));
-    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RC(read_back(ctx, host.data(), ab.p, sizeof(double) * host.size()));
     for (int k = 0; k < m_actual; ++k) alpha[k] = host[k];
     for (int k = 0; k + 1 < m_actual; ++k) beta[k] = host[mm + k];
   } else
@@ -946,14 +898,14 @@ static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, do
   const int nc = dtype == SD_C128 ? 2 : 1;
   // all Krylov vectors are kept complex on the device; a real psi0 keeps exactly-zero imaginary parts
   std::vector<DBuf> V(kry_m);
-  DBuf in, w;
+  DevIn in;
+  DBuf w;
   RC(w.alloc(ctx, 2 * n));
-  const double *inp = (const double *)psi0;
-  if (!on_dev) { RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi0, nc * n)); inp = in.p; }
+  RC(in.stage(ctx, dtype, psi0, on_dev, n));
   int rc = 0;
-  const double norm0 = norm_dev(op, inp, nc * n, &rc); RC(rc);
+  const double norm0 = norm_dev(op, in.p, nc * n, &rc); RC(rc);
   RC(V[0].alloc(ctx, 2 * n));
-  RC(sd_k_promote(ctx, V[0].p, inp, nc, n));
+  RC(sd_k_promote(ctx, V[0].p, in.p, nc, n));
   if (norm0 == 0) {                                                                       // :145-147
     if (log_norm) return sd_set_err(ctx, SD_EZERO, "starting vector has zero norm");
     return emit(V[0].p);
@@ -1001,8 +953,7 @@ static int krylov_evolve_core(Op &op, int dtype, const void *psi0, int64_t n, do
     n2p = n2c; n2c = n2o;
   }
   std::vector<double> hostab(3 * (size_t)kry_m);
-  SD_HIP(ctx, hipMemcpyAsync(hostab.data(), ab.p, sizeof(double) * 3 * (size_t)kry_m, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  RC(read_back(ctx, hostab.data(), ab.p, sizeof(double) * 3 * (size_t)kry_m));
   std::vector<double> alr(kry_m, 0.0), beta(kry_m, 0.0);
   int m_eff = kry_m;
   for (int j = 1; j <= kry_m; ++j) {
@@ -1321,10 +1272,9 @@ int sqw_core(Op &os, int dtype, const void *psi0, bool on_dev, int64_t n, const 
   DBuf psic, phi;
   RC(psic.alloc(ctx, 2 * n)); RC(phi.alloc(ctx, 2 * n));
   {
-    DBuf in;
-    const double *inp = (const double *)psi0;
-    if (!on_dev) { RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi0, nc * n)); inp = in.p; }
-    RC(sd_k_promote(ctx, psic.p, inp, nc, n));                                            // :202
+    DevIn in;
+    RC(in.stage(ctx, dtype, psi0, on_dev, n));
+    RC(sd_k_promote(ctx, psic.p, in.p, nc, n));                                           // :202
   }
   // phi doubles as the scratch for H psi0 (only E0 is kept): the recursion then holds psi0, phi and its three work vectors --
   // five vectors of n elements plus halo and send buffer on a shard
@@ -1343,8 +1293,7 @@ int sqw_core(Op &os, int dtype, const void *psi0, bool on_dev, int64_t n, const 
       RC(sd_k_nrm2sq_to(ctx, phib.p + 2 * nd * k, 2 * nd, nrm.p + 2 * k));
     }
     std::vector<double> hn(2 * (size_t)Qb);
-    SD_HIP(ctx, hipMemcpyAsync(hn.data(), nrm.p, sizeof(double) * hn.size(), hipMemcpyDeviceToHost, ctx->stream));
-    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RC(read_back(ctx, hn.data(), nrm.p, sizeof(double) * hn.size()));
     // zero vectors (:226-229) drop out of the batch; the rest are normalised in place (:231)
     std::vector<double *> kept; std::vector<double> norms;
     for (int k = 0; k < Qb; ++k) {
@@ -1418,13 +1367,12 @@ int spm_q_core(sd_ctx *ctx, const sd_model *src, const sd_model *dst, int op, in
   if (n_src != src->N) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the source basis dimension");
   if (n_dst != dst->N) return sd_set_err(ctx, SD_EDIM, "output length does not match the target basis dimension");
   SD_HIP(ctx, hipSetDevice(ctx->device));
-  if (on_dev) return sd_launch_spm_q(ctx, src, dst, op, dtype_in, psi0, q, phi);
-  const int nc = dtype_in == SD_C128 ? 2 : 1;
-  DBuf in, out;
-  RC(in.alloc(ctx, nc * n_src)); RC(out.alloc(ctx, 2 * n_dst));
-  RC(h2d(ctx, in.p, psi0, nc * n_src));
+  DevIn in;
+  DevOut out;
+  RC(in.stage(ctx, dtype_in, psi0, on_dev, n_src));
+  RC(out.open(ctx, phi, on_dev, 2 * n_dst));
   RC(sd_launch_spm_q(ctx, src, dst, op, dtype_in, in.p, q, out.p));
-  return d2h(ctx, phi, out.p, 2 * n_dst);
+  return out.close(false);                                 // the device form takes nothing from the pool
 }
 // ---- site-resolved KPM moments (the quantity of the reference's src/TimeEvolution/KPM.jl) ----
 // mu_n^{ij} = <psi0| S^z_i T_n(H~) S^z_j |psi0> for the sources j = sources[0..ns) against ALL sites i: per source
@@ -1478,8 +1426,7 @@ int site_moments_dev(Op &op, int dtype, const double *psi0, const int *sources, 
     }
   }
   std::vector<double> hs((size_t)(srow * ns));
-  SD_HIP(ctx, hipMemcpyAsync(hs.data(), res.p, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  RC(read_back(ctx, hs.data(), res.p, sizeof(double) * hs.size()));
   for (int s = 0; s < ns; ++s) {
     const double *h = hs.data() + (size_t)(srow * s);
     const double n0 = h[2 * L];
@@ -1495,42 +1442,28 @@ int site_moments_dev(Op &op, int dtype, const double *psi0, const int *sources, 
   return SD_OK;
 }
 
-// psi0 (host vector, or device rows when on_dev) on the device in its own element type
-int site_stage(sd_ctx *ctx, int dtype, const void *psi0, bool on_dev, int64_t n, DBuf &in, const double **dev) {
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
-  if (!psi0) return sd_set_err(ctx, SD_EARG, "null argument");
-  if (on_dev) { *dev = (const double *)psi0; return SD_OK; }
-  const int nc = dtype == SD_C128 ? 2 : 1;
-  RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi0, nc * n));
-  *dev = in.p;
-  return SD_OK;
-}
-
 int site_project_core(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra, const void *ket, int64_t n, double *out,
                       bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
+  RC(check_unsharded_model(ctx, m));
   if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
   if (!ket || !out) return sd_set_err(ctx, SD_EARG, "null argument");
-  DBuf bin, kin, res;
-  const double *b = nullptr, *k = nullptr;
-  RC(site_stage(ctx, dtype_bra, bra, on_dev, n, bin, &b));
-  RC(site_stage(ctx, SD_C128, ket, on_dev, n, kin, &k));
+  DevIn b, k;
+  DBuf res;
+  RC(b.stage(ctx, dtype_bra, bra, on_dev, n));
+  RC(k.stage(ctx, SD_C128, ket, on_dev, n));
   const int L = m->L;
   RC(res.alloc(ctx, 2 * (int64_t)L + 2));
-  RC(sd_launch_site_project(ctx, m, dtype_bra, b, 0, k, n, 1, res.p, 2 * (int64_t)L + 2));
-  SD_HIP(ctx, hipMemcpyAsync(out, res.p, sizeof(double) * 2 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
+  RC(sd_launch_site_project(ctx, m, dtype_bra, b.p, 0, k.p, n, 1, res.p, 2 * (int64_t)L + 2));
+  return read_back(ctx, out, res.p, sizeof(double) * 2 * (size_t)L);
 }
 
 int site_moments_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const int *sources, int ns, int M,
                       double a, double b, double *mu, bool on_dev) {
   Op op; RC(op.init(ctx, m, nullptr));
   if (n != m->N) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the basis dimension");
-  DBuf in;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi0, on_dev, n, in, &p));
-  return site_moments_dev(op, dtype, p, sources, ns, M, a, b, mu);
+  DevIn in;
+  RC(in.stage(ctx, dtype, psi0, on_dev, n));
+  return site_moments_dev(op, dtype, in.p, sources, ns, M, a, b, mu);
 }
 
 // E0, a, b and the damping factors exactly as kpm_sqw forms them (KpmSpectrum::start), then the site moments of a host psi0
@@ -1541,17 +1474,16 @@ int site_spectral_moments(Op &op, KpmSpectrum &sp, int dtype, const void *psi0, 
   if (n != op.n) return sd_set_err(ctx, SD_EDIM, "psi0 length does not match the basis dimension");
   RC(sp.check());
   if (sp.W > 0 && !sp.omega) return sd_set_err(ctx, SD_EARG, "null argument");
-  DBuf in;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi0, false, n, in, &p));
+  DevIn in;
+  RC(in.stage(ctx, dtype, psi0, false, n));
   {
     DBuf psic, scratch;
     RC(psic.alloc(ctx, 2 * n)); RC(scratch.alloc(ctx, 2 * n));
-    RC(sd_k_promote(ctx, psic.p, p, dtype == SD_C128 ? 2 : 1, n));
+    RC(sd_k_promote(ctx, psic.p, in.p, dtype == SD_C128 ? 2 : 1, n));
     RC(sp.start(op, psic.p, scratch.p));
   }
   mu.assign((size_t)std::max(ns, 0) * (size_t)sp.kpm_m * (size_t)op.m->L * 2, 0.0);
-  return site_moments_dev(op, dtype, p, sources, ns, sp.kpm_m, sp.a, sp.b, mu.data());
+  return site_moments_dev(op, dtype, in.p, sources, ns, sp.kpm_m, sp.a, sp.b, mu.data());
 }
 }  // namespace
 
@@ -1807,13 +1739,13 @@ int imag_evolve_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0
   Op op; RC(op.init(ctx, m, nullptr));
   if (n != op.n) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
   if (!out || !log_norm) return sd_set_err(ctx, SD_EARG, "null argument");
-  DBuf in, vb;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi0, on_dev, n, in, &p));
-  double *v = (double *)out;
-  if (!on_dev) { RC(vb.alloc(ctx, 2 * n)); v = vb.p; }
-  if (dtype == SD_C128 && p == v) { /* in place */ }
-  else RC(sd_k_promote(ctx, v, p, dtype == SD_C128 ? 2 : 1, n));
+  DevIn in;
+  DevOut o;
+  RC(in.stage(ctx, dtype, psi0, on_dev, n));
+  RC(o.open(ctx, out, on_dev, 2 * n));
+  double *v = o.p;
+  if (dtype == SD_C128 && in.p == v) { /* in place */ }
+  else RC(sd_k_promote(ctx, v, in.p, dtype == SD_C128 ? 2 : 1, n));
   if (tau == 0.0) {
     int rc = 0;
     const double nn = norm_dev(op, v, 2 * n, &rc); RC(rc);
@@ -1823,469 +1755,7 @@ int imag_evolve_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0
   } else {
     RC(imag_evolve_dev(op, v, n, tau, method, cheb_n, kry_m, Emin, Emax, 0, log_norm));
   }
-  if (!on_dev) return d2h(ctx, out, v, 2 * n);
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
-}
-
-// the n_hop products w_b t_b on the device (w == null: ones)
-int current_weights(sd_ctx *ctx, const sd_model *m, const double *w, DBuf &wt) {
-  const size_t nh = m->hop_J.size();
-  std::vector<double> h(std::max<size_t>(nh, 1), 0.0);
-  for (size_t b = 0; b < nh; ++b) {
-    if (w && !std::isfinite(w[b])) return sd_set_err(ctx, SD_EARG, "current weights must be finite");
-    h[b] = w ? w[b] * m->hop_J[b] : m->hop_J[b];
-  }
-  RC(wt.alloc(ctx, (int64_t)h.size()));
-  return h2d(ctx, wt.p, h.data(), (int64_t)h.size());
-}
-
-// write form (bra == null): out (ComplexF64, n) = J_w vec; bracket form: out[0..1] (host) = <bra|J_w|vec>, vec ComplexF64
-int current_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, bool bracket, int64_t n, const double *w,
-                 void *out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (!out) return sd_set_err(ctx, SD_EARG, "null argument");
-  if (!bracket && on_dev && out == vec) return sd_set_err(ctx, SD_EARG, "out must not alias psi");
-  DBuf wt, vin, bin, res;
-  const double *v = nullptr, *b = nullptr;
-  RC(current_weights(ctx, m, w, wt));
-  RC(site_stage(ctx, bracket ? SD_C128 : dtype, vec, on_dev, n, vin, &v));
-  if (bracket) {
-    RC(site_stage(ctx, dtype, bra, on_dev, n, bin, &b));
-    RC(res.alloc(ctx, 2));
-    RC(sd_launch_current(ctx, m, dtype, v, b, wt.p, nullptr, res.p));
-    SD_HIP(ctx, hipMemcpyAsync(out, res.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SD_OK;
-  }
-  double *o = (double *)out;
-  if (!on_dev) { RC(res.alloc(ctx, 2 * n)); o = res.p; }
-  RC(sd_launch_current(ctx, m, dtype, v, nullptr, wt.p, o, nullptr));
-  if (!on_dev) return d2h(ctx, out, o, 2 * n);
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));        // the weights go back to the pool
-  return SD_OK;
-}
-
-// A caller's list of dressed bond currents (include/spindyn.h, sd_dterm) validated, cut into groups and put on the device: both
-// tables in one block from the context's pool, the dressed coefficients halved (exact).  n_groups == 0: the empty list.
-struct DList {
-  DBuf buf;
-  int n_groups = 0;
-  const sd_dgroup *groups = nullptr;
-  const sd_dterm_dev *terms = nullptr;
-  int init(sd_ctx *ctx, const sd_model *m, const sd_dterm *list, int n_terms) {
-    if (n_terms < 0 || n_terms > SD_DTERM_MAX) return sd_set_err(ctx, SD_EARG, "the number of terms must be in 0..SD_DTERM_MAX");
-    if (n_terms > 0 && !list) return sd_set_err(ctx, SD_EARG, "null argument");
-    std::vector<sd_dgroup> g;
-    std::vector<sd_dterm_dev> t((size_t)n_terms);
-    for (int n = 0; n < n_terms; ++n) {
-      const sd_dterm &T = list[n];
-      if (T.i < 1 || T.i > m->L || T.j < 1 || T.j > m->L || T.k < 0 || T.k > m->L) return sd_set_err(ctx, SD_EARG, "a site of a term is outside 1..L (k may also be 0)");
-      if (T.i == T.j) return sd_set_err(ctx, SD_EARG, "the two sites of a bond current must differ");
-      if (T.k == T.i || T.k == T.j) return sd_set_err(ctx, SD_EARG, "the S^z site of a term must not be one of its bond's sites");
-      if (!std::isfinite(T.c)) return sd_set_err(ctx, SD_EARG, "the coefficients must be finite");
-      if (n == 0 || T.i != list[n - 1].i || T.j != list[n - 1].j) {
-        const int lo = std::min(T.i, T.j) - 1, hi = std::max(T.i, T.j) - 1;
-        g.push_back(sd_dgroup{lo | (hi << 8) | ((T.i > T.j ? 1 : 0) << 16), n, 0, 0});
-      }
-      ++g.back().count;
-      t[(size_t)n] = sd_dterm_dev{T.k == 0 ? T.c : 0.5 * T.c, T.k - 1, 0};
-    }
-    n_groups = (int)g.size();
-    if (n_groups == 0) return SD_OK;
-    static_assert(sizeof(sd_dgroup) == 16 && sizeof(sd_dterm_dev) == 16, "table layout");
-    RC(buf.alloc(ctx, 2 * (int64_t)(g.size() + t.size())));
-    groups = (const sd_dgroup *)buf.p;
-    terms = (const sd_dterm_dev *)(buf.p + 2 * g.size());
-    RC(sd_xfer_h2d(ctx, buf.p, g.data(), sizeof(sd_dgroup) * g.size()));
-    return sd_xfer_h2d(ctx, buf.p + 2 * g.size(), t.data(), sizeof(sd_dterm_dev) * t.size());
-  }
-};
-
-// write form (bra == null): out (ComplexF64, n) = J vec; bracket form: out[0..1] (host) = <bra|J|vec>, vec ComplexF64
-int dcurrent_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *vec, const void *bra, bool bracket, int64_t n,
-                  const sd_dterm *list, int n_terms, void *out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (!out || !vec) return sd_set_err(ctx, SD_EARG, "null argument");
-  if (!bracket && on_dev && out == vec) return sd_set_err(ctx, SD_EARG, "out must not alias psi");
-  DList dl;
-  RC(dl.init(ctx, m, list, n_terms));
-  DBuf vin, bin, res;
-  const double *v = nullptr, *b = nullptr;
-  RC(site_stage(ctx, bracket ? SD_C128 : dtype, vec, on_dev, n, vin, &v));
-  if (bracket) {
-    RC(site_stage(ctx, dtype, bra, on_dev, n, bin, &b));
-    RC(res.alloc(ctx, 2));
-    RC(sd_launch_dcurrent(ctx, m, dtype, v, b, dl.groups, dl.n_groups, dl.terms, nullptr, res.p));
-    SD_HIP(ctx, hipMemcpyAsync(out, res.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SD_OK;
-  }
-  double *o = (double *)out;
-  if (!on_dev) { RC(res.alloc(ctx, 2 * n)); o = res.p; }
-  RC(sd_launch_dcurrent(ctx, m, dtype, v, nullptr, dl.groups, dl.n_groups, dl.terms, o, nullptr));
-  if (!on_dev) return d2h(ctx, out, o, 2 * n);
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));        // the tables go back to the pool
-  return SD_OK;
-}
-
-// M_out (host, 2 L L doubles) = the L x L pair-correlation matrix of psi: the kernel sums the pairs i <= j, the other triangle is
-// the conjugate
-int pair_correlations_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int component, double *M_out,
-                           bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (component != SD_PAIR_ZZ && component != SD_PAIR_PM) return sd_set_err(ctx, SD_EARG, "component must be SD_PAIR_ZZ or SD_PAIR_PM");
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (!M_out) return sd_set_err(ctx, SD_EARG, "null argument");
-  DBuf in, plist, res;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
-  const int L = m->L;
-  std::vector<int> pairs;
-  for (int i = 0; i < L; ++i)
-    for (int j = i; j < L; ++j) pairs.push_back(i | (j << 8));
-  const int np = (int)pairs.size();
-  RC(plist.alloc(ctx, (np + 1) / 2));
-  RC(sd_xfer_h2d(ctx, plist.p, pairs.data(), sizeof(int) * (size_t)np));
-  RC(res.alloc(ctx, 2 * (int64_t)np));
-  RC(sd_launch_pair_correlations(ctx, m, dtype, p, component, (const int *)plist.p, np, res.p));
-  std::vector<double> h(2 * (size_t)np);
-  SD_HIP(ctx, hipMemcpyAsync(h.data(), res.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (int k = 0; k < np; ++k) {
-    const int i = pairs[k] & 255, j = pairs[k] >> 8;
-    const double re = h[2 * (size_t)k], im = h[2 * (size_t)k + 1];
-    double *a = M_out + 2 * ((size_t)i * L + j), *b = M_out + 2 * ((size_t)j * L + i);
-    b[0] = re; b[1] = im == 0.0 ? 0.0 : -im;
-    a[0] = re; a[1] = im;
-  }
-  return SD_OK;
-}
-
-// ---- S^z-basis statistics (kernels_basis_stats.hip) ----
-int basis_moments_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const double *q, int nq, double *out,
-                       bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (!out || (nq > 0 && !q)) return sd_set_err(ctx, SD_EARG, "null argument");
-  if (nq < 0 || nq > SD_MOMENT_MAX_Q) return sd_set_err(ctx, SD_EARG, "basis moments: between 0 and SD_MOMENT_MAX_Q exponents");
-  DBuf in, res;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
-  RC(res.alloc(ctx, 5 + SD_MOMENT_MAX_Q));
-  RC(sd_launch_basis_moments(ctx, m, dtype, p, q, nq, res.p));
-  SD_HIP(ctx, hipMemcpyAsync(out, res.p, sizeof(double) * (size_t)(5 + nq), hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
-}
-
-int counting_statistics_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const uint64_t *masks, int K,
-                             double *P_out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (!P_out || !masks) return sd_set_err(ctx, SD_EARG, "null argument");
-  if (K < 1 || K > SD_COUNT_MAX_MASKS) return sd_set_err(ctx, SD_EARG, "counting statistics: between 1 and SD_COUNT_MAX_MASKS masks");
-  DBuf in, res;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
-  const int64_t np = (int64_t)K * (m->L + 1);
-  RC(res.alloc(ctx, np));
-  RC(sd_launch_counting_statistics(ctx, m, dtype, p, masks, K, res.p));
-  SD_HIP(ctx, hipMemcpyAsync(P_out, res.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
-}
-
-int sample_configurations_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int64_t shots, uint64_t seed,
-                               int64_t *rows_out, uint64_t *configs_out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (shots < 0) return sd_set_err(ctx, SD_EARG, "snapshots: a negative number of shots");
-  if (shots > 0 && !configs_out) return sd_set_err(ctx, SD_EARG, "null argument");
-  DBuf in, res;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
-  RC(res.alloc(ctx, 2 * std::max<int64_t>(shots, 1)));     // rows, then configurations: 8 bytes each
-  int64_t *rows_dev = (int64_t *)res.p;
-  uint64_t *cfg_dev = (uint64_t *)(res.p + std::max<int64_t>(shots, 1));
-  RC(sd_launch_sample_configurations(ctx, m, dtype, p, shots, seed, rows_dev, cfg_dev));
-  if (shots == 0) return SD_OK;
-  if (rows_out) SD_HIP(ctx, hipMemcpyAsync(rows_out, rows_dev, sizeof(int64_t) * (size_t)shots, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipMemcpyAsync(configs_out, cfg_dev, sizeof(uint64_t) * (size_t)shots, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
-}
-
-// the 0-based bits lo < hi of the bond of the 1-based sites (i, j): D_b is symmetric in its two sites
-int bond_bits(sd_ctx *ctx, const sd_model *m, int i, int j, int *lo, int *hi) {
-  if (i < 1 || i > m->L || j < 1 || j > m->L) return sd_set_err(ctx, SD_EARG, "a bond site is outside 1..L");
-  if (i == j) return sd_set_err(ctx, SD_EARG, "the two sites of a bond must differ");
-  *lo = std::min(i, j) - 1; *hi = std::max(i, j) - 1;
-  return SD_OK;
-}
-
-// out (n elements of psi's dtype) = D_b psi, b = (i, j)
-int bond_apply_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int i, int j, double xy, double zz, void *out,
-                    bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  int lo = 0, hi = 0;
-  RC(bond_bits(ctx, m, i, j, &lo, &hi));
-  if (!std::isfinite(xy) || !std::isfinite(zz)) return sd_set_err(ctx, SD_EARG, "the bond weights must be finite");
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (!out) return sd_set_err(ctx, SD_EARG, "null argument");
-  if (on_dev && out == psi) return sd_set_err(ctx, SD_EARG, "out must not alias psi");
-  DBuf in, res;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
-  const int nc = dtype == SD_C128 ? 2 : 1;
-  double *o = (double *)out;
-  if (!on_dev) { RC(res.alloc(ctx, nc * n)); o = res.p; }
-  RC(sd_launch_bond_apply(ctx, m, dtype, p, lo, hi, xy, zz, o));
-  if (!on_dev) return d2h(ctx, out, o, nc * n);
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
-}
-
-// D_out (host, 2 B B doubles) = the B x B dimer matrix of psi, e_out (host, B doubles) the bond expectation values: the kernel sums
-// the tiles of the upper triangle of 4-bond chunks (inside a diagonal tile a <= b is used), the other triangle is the conjugate
-int dimer_correlations_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const int *bonds, int B, double xy,
-                            double zz, double *D_out, double *e_out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (B < 1 || B > SD_DIMER_MAX_BONDS) return sd_set_err(ctx, SD_EARG, "the number of bonds must be in 1..SD_DIMER_MAX_BONDS");
-  if (!bonds || !D_out || !e_out) return sd_set_err(ctx, SD_EARG, "null argument");
-  std::vector<int> packed((size_t)B);
-  for (int b = 0; b < B; ++b) {
-    int lo = 0, hi = 0;
-    RC(bond_bits(ctx, m, bonds[2 * b], bonds[2 * b + 1], &lo, &hi));
-    packed[(size_t)b] = lo | (hi << 8);
-  }
-  if (!std::isfinite(xy) || !std::isfinite(zz)) return sd_set_err(ctx, SD_EARG, "the bond weights must be finite");
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  DBuf in, blist, res;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
-  RC(blist.alloc(ctx, (B + 1) / 2));
-  RC(sd_xfer_h2d(ctx, blist.p, packed.data(), sizeof(int) * (size_t)B));
-  const int ntiles = sd_dimer_tiles(B), nch = (B + 3) / 4;
-  RC(res.alloc(ctx, (int64_t)ntiles * SD_DIMER_TILE_ROW));
-  RC(sd_launch_dimer_gram(ctx, m, dtype, p, (const int *)blist.p, B, xy, zz, res.p));
-  std::vector<double> h((size_t)ntiles * SD_DIMER_TILE_ROW);
-  SD_HIP(ctx, hipMemcpyAsync(h.data(), res.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  size_t t = 0;
-  for (int ca = 0; ca < nch; ++ca)
-    for (int cb = ca; cb < nch; ++cb, ++t) {
-      const double *row = h.data() + t * SD_DIMER_TILE_ROW;
-      for (int ka = 0; ka < 4 && 4 * ca + ka < B; ++ka) {
-        const int a = 4 * ca + ka;
-        if (ca == cb) e_out[a] = row[32 + ka];
-        for (int kb = (ca == cb ? ka : 0); kb < 4 && 4 * cb + kb < B; ++kb) {
-          const int b = 4 * cb + kb;
-          const double re = row[2 * (4 * ka + kb)], im = row[2 * (4 * ka + kb) + 1];
-          double *up = D_out + 2 * ((size_t)a * B + b), *dn = D_out + 2 * ((size_t)b * B + a);
-          dn[0] = re; dn[1] = im == 0.0 ? 0.0 : -im;
-          up[0] = re; up[1] = im;
-        }
-      }
-    }
-  return SD_OK;
-}
-
-// ---- lattice symmetry operators (kernels_symmetry.hip) ----
-// do the byte ranges [a, a + na) and [b, b + nb) share a byte?  (the gathers read rows of psi that other workgroups' rows of out
-// would overwrite: any overlap corrupts the result, not only out == psi)
-bool sym_overlap(const void *a, size_t na, const void *b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
-int sym_code(sd_ctx *ctx, const sd_model *m, int code) {
-  std::string err;
-  const int rc = sd_symmetry_check_code(m, code, err);
-  return rc ? sd_set_err(ctx, rc, err) : SD_OK;
-}
-
-// a validated element list on the device: the coefficients (2 n doubles, when given) first, then the n codes
-struct SymList {
-  DBuf buf;
-  const int *codes = nullptr;
-  const double *coef = nullptr;
-  bool all_real = true;
-  int init(sd_ctx *ctx, const sd_model *m, const int *list, const double *c, int n) {
-    if (n < 1 || n > SD_SYM_MAX_ELEMENTS) return sd_set_err(ctx, SD_EARG, "the number of elements must be in 1..SD_SYM_MAX_ELEMENTS");
-    if (!list) return sd_set_err(ctx, SD_EARG, "null argument");
-    for (int k = 0; k < n; ++k) {
-      RC(sym_code(ctx, m, list[k]));
-      if (c && (!std::isfinite(c[2 * k]) || !std::isfinite(c[2 * k + 1]))) return sd_set_err(ctx, SD_EARG, "the coefficients must be finite");
-      if (c && c[2 * k + 1] != 0.0) all_real = false;
-    }
-    const int64_t nc = c ? 2 * (int64_t)n : 0;
-    RC(buf.alloc(ctx, nc + (n + 1) / 2));
-    if (c) RC(h2d(ctx, buf.p, c, nc));
-    RC(sd_xfer_h2d(ctx, buf.p + nc, list, sizeof(int) * (size_t)n));
-    coef = buf.p;
-    codes = (const int *)(buf.p + nc);
-    return SD_OK;
-  }
-};
-
-// out (n elements of psi's dtype) = U_g psi (+ c y)
-int symmetry_apply_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, int code, const void *y, double cr,
-                        double ci, void *out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  RC(sym_code(ctx, m, code));
-  if (y && (!std::isfinite(cr) || !std::isfinite(ci))) return sd_set_err(ctx, SD_EARG, "the coefficient must be finite");
-  if (y && dtype == SD_F64 && ci != 0.0) return sd_set_err(ctx, SD_EARG, "a Float64 vector takes a real coefficient (c_im = 0)");
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (!out || !psi) return sd_set_err(ctx, SD_EARG, "null argument");
-  const size_t vbytes = (size_t)n * (dtype == SD_C128 ? 16 : 8);
-  if (on_dev && sym_overlap(out, vbytes, psi, vbytes)) return sd_set_err(ctx, SD_EARG, "out must not alias or overlap psi");
-  if (on_dev && y && y != out && sym_overlap(out, vbytes, y, vbytes)) return sd_set_err(ctx, SD_EARG, "out may be y itself but must not overlap it partly");
-  DBuf in, yin, res;
-  const double *p = nullptr, *yp = nullptr;
-  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
-  if (y) RC(site_stage(ctx, dtype, y, on_dev, n, yin, &yp));
-  const int nc = dtype == SD_C128 ? 2 : 1;
-  double *o = (double *)out;
-  if (!on_dev) { RC(res.alloc(ctx, nc * n)); o = res.p; }
-  RC(sd_launch_symmetry_apply(ctx, m, dtype, code, p, yp, cr, ci, o));
-  if (!on_dev) return d2h(ctx, out, o, nc * n);
-  return SD_OK;
-}
-
-// out (host, 2 n_codes doubles) = <bra|U_g|ket> for the elements of the list
-int symmetry_overlaps_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra, const void *ket, int64_t n, const int *codes,
-                           int n_codes, double *out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (!ket || !out) return sd_set_err(ctx, SD_EARG, "null argument");
-  SymList sl;
-  RC(sl.init(ctx, m, codes, nullptr, n_codes));
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  DBuf bin, kin, res;
-  const double *b = nullptr, *k = nullptr;
-  RC(site_stage(ctx, dtype, ket, on_dev, n, kin, &k));
-  b = k;
-  if (bra && bra != ket) RC(site_stage(ctx, dtype, bra, on_dev, n, bin, &b));
-  RC(res.alloc(ctx, 2 * (int64_t)n_codes));
-  RC(sd_launch_symmetry_overlaps(ctx, m, dtype, b, k, sl.codes, n_codes, res.p));
-  SD_HIP(ctx, hipMemcpyAsync(out, res.p, sizeof(double) * 2 * (size_t)n_codes, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
-}
-
-// out (n elements of dtype_out) = sum_k c_k U_{g_k} psi
-int symmetry_project_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const int *codes, const double *coef,
-                          int n_codes, int dtype_out, void *out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (dtype_out != SD_F64 && dtype_out != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype_out must be SD_F64 or SD_C128");
-  if (!coef || !out || !psi) return sd_set_err(ctx, SD_EARG, "null argument");
-  SymList sl;
-  RC(sl.init(ctx, m, codes, coef, n_codes));
-  if (dtype_out == SD_F64 && dtype != SD_F64) return sd_set_err(ctx, SD_EARG, "an SD_F64 result needs an SD_F64 psi");
-  if (dtype_out == SD_F64 && !sl.all_real) return sd_set_err(ctx, SD_EARG, "an SD_F64 result needs real coefficients");
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (on_dev && sym_overlap(out, (size_t)n * (dtype_out == SD_C128 ? 16 : 8), psi, (size_t)n * (dtype == SD_C128 ? 16 : 8))) return sd_set_err(ctx, SD_EARG, "out must not alias or overlap psi");
-  DBuf in, res;
-  const double *p = nullptr;
-  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
-  const int nc = dtype_out == SD_C128 ? 2 : 1;
-  double *o = (double *)out;
-  if (!on_dev) { RC(res.alloc(ctx, nc * n)); o = res.p; }
-  RC(sd_launch_symmetry_project(ctx, m, dtype, p, sl.codes, sl.coef, n_codes, dtype_out, o));
-  if (!on_dev) return d2h(ctx, out, o, nc * n);
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));        // the list goes back to the pool
-  return SD_OK;
-}
-
-// ---- operator strings (kernels_opstring.hip) ----
-// A caller's list validated, cut into groups and put on the device: the three tables in one block from the context's pool (groups, 4
-// doubles each; terms, 3 doubles each; op_first).  n_groups == 0: the empty list.
-struct OpList {
-  DBuf buf;
-  sd_opstring_tables tab;
-  int n_groups = 0;
-  const sd_opgroup *groups = nullptr;
-  const sd_opterm_dev *terms = nullptr;
-  const int32_t *op_first = nullptr;
-  int init(sd_ctx *ctx, const sd_model *m, const sd_opterm *list, int n_terms) {
-    std::string err;
-    const int rc = sd_opstring_build(m, list, n_terms, tab, err);
-    if (rc) return sd_set_err(ctx, rc, err);
-    n_groups = (int)tab.groups.size();
-    if (n_groups == 0) return SD_OK;
-    static_assert(sizeof(sd_opgroup) == 32 && sizeof(sd_opterm_dev) == 24, "table layout");
-    const int64_t ng = 4 * (int64_t)tab.groups.size(), nt = 3 * (int64_t)tab.terms.size();
-    RC(buf.alloc(ctx, ng + nt + ((int64_t)tab.op_first.size() + 1) / 2));
-    groups = (const sd_opgroup *)buf.p;
-    terms = (const sd_opterm_dev *)(buf.p + ng);
-    op_first = (const int32_t *)(buf.p + ng + nt);
-    RC(sd_xfer_h2d(ctx, buf.p, tab.groups.data(), sizeof(sd_opgroup) * tab.groups.size()));
-    RC(sd_xfer_h2d(ctx, buf.p + ng, tab.terms.data(), sizeof(sd_opterm_dev) * tab.terms.size()));
-    return sd_xfer_h2d(ctx, buf.p + ng + nt, tab.op_first.data(), sizeof(int32_t) * tab.op_first.size());
-  }
-};
-
-// out (n elements of dtype_out) = O_0 psi (+ (b_re + i b_im) y, y of dtype_out)
-int opstring_apply_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const sd_opterm *list, int n_terms,
-                        const void *y, double b_re, double b_im, int dtype_out, void *out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  if (dtype_out != SD_F64 && dtype_out != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype_out must be SD_F64 or SD_C128");
-  OpList ol;
-  RC(ol.init(ctx, m, list, n_terms));
-  for (int k = 0; k < n_terms; ++k)
-    if (list[k].op != 0) return sd_set_err(ctx, SD_EARG, "the write form takes one operator: every term must have op = 0");
-  if (y && (!std::isfinite(b_re) || !std::isfinite(b_im))) return sd_set_err(ctx, SD_EARG, "the coefficient b must be finite");
-  if (dtype_out == SD_F64 && dtype != SD_F64) return sd_set_err(ctx, SD_EARG, "an SD_F64 output needs an SD_F64 psi");
-  if (dtype_out == SD_F64 && !ol.tab.all_real) return sd_set_err(ctx, SD_EARG, "an SD_F64 output needs real coefficients (every c_im = 0)");
-  if (dtype_out == SD_F64 && y && b_im != 0.0) return sd_set_err(ctx, SD_EARG, "an SD_F64 output takes a real b (b_im = 0)");
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (!out || !psi) return sd_set_err(ctx, SD_EARG, "null argument");
-  const int nco = dtype_out == SD_C128 ? 2 : 1;
-  const size_t obytes = (size_t)n * 8 * (size_t)nco, pbytes = (size_t)n * (dtype == SD_C128 ? 16 : 8);
-  if (on_dev && sym_overlap(out, obytes, psi, pbytes)) return sd_set_err(ctx, SD_EARG, "out must not alias or overlap psi");
-  if (on_dev && y && y != out && sym_overlap(out, obytes, y, obytes)) return sd_set_err(ctx, SD_EARG, "out may be y itself but must not overlap it partly");
-  DBuf in, yin, res;
-  const double *p = nullptr, *yp = nullptr;
-  RC(site_stage(ctx, dtype, psi, on_dev, n, in, &p));
-  if (y) RC(site_stage(ctx, dtype_out, y, on_dev, n, yin, &yp));
-  double *o = (double *)out;
-  if (!on_dev) { RC(res.alloc(ctx, nco * n)); o = res.p; }
-  RC(sd_launch_opstring(ctx, m, dtype, p, ol.groups, ol.n_groups, ol.terms, yp, b_re, b_im, dtype_out, o));
-  if (!on_dev) return d2h(ctx, out, o, nco * n);
-  if (ol.n_groups > 0) SD_HIP(ctx, hipStreamSynchronize(ctx->stream));        // the tables go back to the pool
-  return SD_OK;
-}
-
-// out (host, 2 K doubles, K = 1 + max op) = <bra|O_k|ket>
-int opstring_expect_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra, const void *ket, int64_t n, const sd_opterm *list,
-                         int n_terms, double *out, bool on_dev) {
-  Op op; RC(op.init(ctx, m, nullptr));
-  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
-  OpList ol;
-  RC(ol.init(ctx, m, list, n_terms));
-  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
-  if (!ket) return sd_set_err(ctx, SD_EARG, "null argument");
-  const int K = ol.tab.n_ops;
-  if (K == 0) return SD_OK;                                  // the empty list: no operator, nothing to write
-  if (!out) return sd_set_err(ctx, SD_EARG, "null argument");
-  DBuf bin, kin, res;
-  const double *b = nullptr, *k = nullptr;
-  RC(site_stage(ctx, dtype, ket, on_dev, n, kin, &k));
-  b = k;
-  if (bra && bra != ket) RC(site_stage(ctx, dtype, bra, on_dev, n, bin, &b));
-  RC(res.alloc(ctx, 2 * (int64_t)K));
-  RC(sd_launch_opstring_expect(ctx, m, dtype, b, k, ol.groups, ol.op_first, ol.terms, K, res.p));
-  SD_HIP(ctx, hipMemcpyAsync(out, res.p, sizeof(double) * 2 * (size_t)K, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
+  return o.close(true);                                    // the work vectors go back to the pool
 }
 
 // an operator of the typicality driver: kind, site or momentum, device weights of a current, device tables of the energy current
@@ -2339,211 +1809,6 @@ extern "C" int sd_imag_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const v
 extern "C" int sd_imag_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, double tau, int method,
                                   int cheb_n, int kry_m, double Emin, double Emax, void *out_dev, double *log_norm) {
   return abi_guard(ctx, [&]() -> int { return imag_evolve_core(ctx, m, dtype, psi0_dev, n, tau, method, cheb_n, kry_m, Emin, Emax, out_dev, log_norm, true); });
-}
-
-extern "C" int sd_current_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const double *w,
-                                void *out_host) {
-  return abi_guard(ctx, [&]() -> int { return current_core(ctx, m, dtype, psi_host, nullptr, false, n, w, out_host, false); });
-}
-extern "C" int sd_current_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const double *w,
-                                    void *out_dev) {
-  return abi_guard(ctx, [&]() -> int { return current_core(ctx, m, dtype, psi_dev, nullptr, false, n, w, out_dev, true); });
-}
-extern "C" int sd_current_bracket(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_host, const void *ket_host, int64_t n,
-                                  const double *w, double *out) {
-  return abi_guard(ctx, [&]() -> int {
-    if (!bra_host) return sd_set_err(ctx, SD_EARG, "null argument");
-    return current_core(ctx, m, dtype_bra, ket_host, bra_host, true, n, w, out, false);
-  });
-}
-extern "C" int sd_current_bracket_dev(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_dev, const void *ket_dev, int64_t n,
-                                      const double *w, double *out) {
-  return abi_guard(ctx, [&]() -> int {
-    if (!bra_dev) return sd_set_err(ctx, SD_EARG, "null argument");
-    return current_core(ctx, m, dtype_bra, ket_dev, bra_dev, true, n, w, out, true);
-  });
-}
-
-extern "C" int sd_energy_current_terms(const sd_model *m, int periodic, sd_dterm *out, int cap, int *n_terms) {
-  return abi_guard(nullptr, [&]() -> int {
-    if (!m || !n_terms || cap < 0 || (cap > 0 && !out) || (periodic != 0 && periodic != 1)) return SD_EARG;
-    std::vector<sd_dterm> list;
-    std::string err;
-    const int rc = sd_build_energy_current(m, periodic, list, err);
-    if (rc) return m->ctx ? sd_set_err(m->ctx, rc, err) : rc;
-    *n_terms = (int)list.size();
-    if (cap == 0) return SD_OK;
-    if ((size_t)cap < list.size()) return m->ctx ? sd_set_err(m->ctx, SD_EARG, "cap is smaller than the number of terms") : SD_EARG;
-    std::copy(list.begin(), list.end(), out);
-    return SD_OK;
-  });
-}
-extern "C" int sd_dcurrent_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_dterm *terms,
-                                 int n_terms, void *out_host) {
-  return abi_guard(ctx, [&]() -> int { return dcurrent_core(ctx, m, dtype, psi_host, nullptr, false, n, terms, n_terms, out_host, false); });
-}
-extern "C" int sd_dcurrent_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_dterm *terms,
-                                     int n_terms, void *out_dev) {
-  return abi_guard(ctx, [&]() -> int { return dcurrent_core(ctx, m, dtype, psi_dev, nullptr, false, n, terms, n_terms, out_dev, true); });
-}
-extern "C" int sd_dcurrent_bracket(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_host, const void *ket_host, int64_t n,
-                                   const sd_dterm *terms, int n_terms, double *out) {
-  return abi_guard(ctx, [&]() -> int {
-    if (!bra_host) return sd_set_err(ctx, SD_EARG, "null argument");
-    return dcurrent_core(ctx, m, dtype_bra, ket_host, bra_host, true, n, terms, n_terms, out, false);
-  });
-}
-extern "C" int sd_dcurrent_bracket_dev(sd_ctx *ctx, const sd_model *m, int dtype_bra, const void *bra_dev, const void *ket_dev, int64_t n,
-                                       const sd_dterm *terms, int n_terms, double *out) {
-  return abi_guard(ctx, [&]() -> int {
-    if (!bra_dev) return sd_set_err(ctx, SD_EARG, "null argument");
-    return dcurrent_core(ctx, m, dtype_bra, ket_dev, bra_dev, true, n, terms, n_terms, out, true);
-  });
-}
-
-extern "C" int sd_pair_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int component,
-                                    double *M_out) {
-  return abi_guard(ctx, [&]() -> int { return pair_correlations_core(ctx, m, dtype, psi_host, n, component, M_out, false); });
-}
-extern "C" int sd_pair_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int component,
-                                        double *M_out) {
-  return abi_guard(ctx, [&]() -> int { return pair_correlations_core(ctx, m, dtype, psi_dev, n, component, M_out, true); });
-}
-
-extern "C" int sd_basis_moments(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const double *q, int nq,
-                                double *out) {
-  return abi_guard(ctx, [&]() -> int { return basis_moments_core(ctx, m, dtype, psi_host, n, q, nq, out, false); });
-}
-extern "C" int sd_basis_moments_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const double *q, int nq,
-                                    double *out) {
-  return abi_guard(ctx, [&]() -> int { return basis_moments_core(ctx, m, dtype, psi_dev, n, q, nq, out, true); });
-}
-extern "C" int sd_counting_range(const sd_model *m, uint64_t mask, int *m_min, int *n_bins) {
-  if (!m || !m_min || !n_bins) return SD_EARG;
-  return sd_counting_range_host(m, mask, m_min, n_bins);
-}
-extern "C" int sd_counting_statistics(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const uint64_t *masks,
-                                      int K, double *P_out) {
-  return abi_guard(ctx, [&]() -> int { return counting_statistics_core(ctx, m, dtype, psi_host, n, masks, K, P_out, false); });
-}
-extern "C" int sd_counting_statistics_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n,
-                                          const uint64_t *masks, int K, double *P_out) {
-  return abi_guard(ctx, [&]() -> int { return counting_statistics_core(ctx, m, dtype, psi_dev, n, masks, K, P_out, true); });
-}
-extern "C" int sd_sample_uniforms_host(uint64_t seed, uint64_t first, int64_t n, double *u_out) {
-  if (!u_out || n < 0) return SD_EARG;
-  for (int64_t i = 0; i < n; ++i) u_out[i] = sd_sample_uniform_host(seed, first + (uint64_t)i);
-  return SD_OK;
-}
-extern "C" int sd_sample_configurations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int64_t shots,
-                                        uint64_t seed, int64_t *rows_out, uint64_t *configs_out) {
-  return abi_guard(ctx, [&]() -> int {
-    return sample_configurations_core(ctx, m, dtype, psi_host, n, shots, seed, rows_out, configs_out, false);
-  });
-}
-extern "C" int sd_sample_configurations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int64_t shots,
-                                            uint64_t seed, int64_t *rows_out, uint64_t *configs_out) {
-  return abi_guard(ctx, [&]() -> int {
-    return sample_configurations_core(ctx, m, dtype, psi_dev, n, shots, seed, rows_out, configs_out, true);
-  });
-}
-
-extern "C" int sd_bond_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int i, int j, double xy,
-                             double zz, void *out_host) {
-  return abi_guard(ctx, [&]() -> int { return bond_apply_core(ctx, m, dtype, psi_host, n, i, j, xy, zz, out_host, false); });
-}
-extern "C" int sd_bond_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int i, int j, double xy,
-                                 double zz, void *out_dev) {
-  return abi_guard(ctx, [&]() -> int { return bond_apply_core(ctx, m, dtype, psi_dev, n, i, j, xy, zz, out_dev, true); });
-}
-extern "C" int sd_dimer_correlations(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *bonds,
-                                     int B, double xy, double zz, double *D_out, double *e_out) {
-  return abi_guard(ctx, [&]() -> int { return dimer_correlations_core(ctx, m, dtype, psi_host, n, bonds, B, xy, zz, D_out, e_out, false); });
-}
-extern "C" int sd_dimer_correlations_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *bonds,
-                                         int B, double xy, double zz, double *D_out, double *e_out) {
-  return abi_guard(ctx, [&]() -> int { return dimer_correlations_core(ctx, m, dtype, psi_dev, n, bonds, B, xy, zz, D_out, e_out, true); });
-}
-
-extern "C" int sd_symmetry_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, int code, const void *y_host,
-                                 double c_re, double c_im, void *out_host) {
-  return abi_guard(ctx, [&]() -> int { return symmetry_apply_core(ctx, m, dtype, psi_host, n, code, y_host, c_re, c_im, out_host, false); });
-}
-extern "C" int sd_symmetry_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, int code,
-                                     const void *y_dev, double c_re, double c_im, void *out_dev) {
-  return abi_guard(ctx, [&]() -> int { return symmetry_apply_core(ctx, m, dtype, psi_dev, n, code, y_dev, c_re, c_im, out_dev, true); });
-}
-extern "C" int sd_symmetry_overlaps(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_host, const void *ket_host, int64_t n,
-                                    const int *codes, int n_codes, double *out) {
-  return abi_guard(ctx, [&]() -> int { return symmetry_overlaps_core(ctx, m, dtype, bra_host, ket_host, n, codes, n_codes, out, false); });
-}
-extern "C" int sd_symmetry_overlaps_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_dev, const void *ket_dev, int64_t n,
-                                        const int *codes, int n_codes, double *out) {
-  return abi_guard(ctx, [&]() -> int { return symmetry_overlaps_core(ctx, m, dtype, bra_dev, ket_dev, n, codes, n_codes, out, true); });
-}
-extern "C" int sd_symmetry_project(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const int *codes,
-                                   const double *coef, int n_codes, int dtype_out, void *out_host) {
-  return abi_guard(ctx, [&]() -> int { return symmetry_project_core(ctx, m, dtype, psi_host, n, codes, coef, n_codes, dtype_out, out_host, false); });
-}
-extern "C" int sd_symmetry_project_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const int *codes,
-                                       const double *coef, int n_codes, int dtype_out, void *out_dev) {
-  return abi_guard(ctx, [&]() -> int { return symmetry_project_core(ctx, m, dtype, psi_dev, n, codes, coef, n_codes, dtype_out, out_dev, true); });
-}
-
-extern "C" int sd_opstring_check(const sd_model *m, const sd_opterm *terms, int n_terms, int *n_ops, int *hermitian) {
-  return abi_guard(nullptr, [&]() -> int {
-    if (!m || !n_ops || !hermitian) return SD_EARG;
-    sd_opstring_tables tab;
-    std::string err;
-    const int rc = sd_opstring_build(m, terms, n_terms, tab, err);
-    if (rc) return m->ctx ? sd_set_err(m->ctx, rc, err) : rc;
-    *n_ops = tab.n_ops;
-    *hermitian = sd_opstring_hermitian(terms, n_terms) ? 1 : 0;
-    return SD_OK;
-  });
-}
-extern "C" int sd_hamiltonian_terms(const sd_model *m, sd_opterm *out, int cap, int *n_terms) {
-  return abi_guard(nullptr, [&]() -> int {
-    if (!m || !n_terms || cap < 0 || (cap > 0 && !out)) return SD_EARG;
-    auto fail = [&](const char *msg) { return m->ctx ? sd_set_err(m->ctx, SD_EARG, msg) : SD_EARG; };
-    if (m->L < 1 || m->L > SD_MAX_L) return fail("operator strings need 1 <= L <= 63");
-    auto bit = [](int site) { return (uint64_t)1 << (site - 1); };
-    std::vector<sd_opterm> list;
-    for (size_t b = 0; b < m->hop_J.size(); ++b) {           // t (S^+_i S^-_j + S^-_i S^+_j); i == j never flips
-      const int i = m->hop_i[b], j = m->hop_j[b];
-      if (i == j) continue;
-      list.push_back(sd_opterm{bit(i), bit(j), 0, m->hop_J[b], 0.0, 0, 0});
-      list.push_back(sd_opterm{bit(j), bit(i), 0, m->hop_J[b], 0.0, 0, 0});
-    }
-    for (size_t b = 0; b < m->zz_J.size(); ++b) {            // v S^z_i S^z_j; i == j: (S^z_i)^2 = 1/4
-      const int i = m->zz_i[b], j = m->zz_j[b];
-      if (i == j) list.push_back(sd_opterm{0, 0, 0, 0.25 * m->zz_J[b], 0.0, 0, 0});
-      else list.push_back(sd_opterm{0, 0, bit(i) | bit(j), m->zz_J[b], 0.0, 0, 0});
-    }
-    for (int i = 1; i <= m->L && i <= (int)m->field.size(); ++i) list.push_back(sd_opterm{0, 0, bit(i), m->field[(size_t)i - 1], 0.0, 0, 0});
-    if (list.size() > SD_OPTERM_MAX) return fail("the model's lists give more than SD_OPTERM_MAX terms");
-    *n_terms = (int)list.size();
-    if (cap == 0) return SD_OK;
-    if ((size_t)cap < list.size()) return fail("cap is smaller than the number of terms");
-    std::copy(list.begin(), list.end(), out);
-    return SD_OK;
-  });
-}
-extern "C" int sd_opstring_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_opterm *terms,
-                                 int n_terms, const void *y_host, double b_re, double b_im, int dtype_out, void *out_host) {
-  return abi_guard(ctx, [&]() -> int { return opstring_apply_core(ctx, m, dtype, psi_host, n, terms, n_terms, y_host, b_re, b_im, dtype_out, out_host, false); });
-}
-extern "C" int sd_opstring_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_opterm *terms,
-                                     int n_terms, const void *y_dev, double b_re, double b_im, int dtype_out, void *out_dev) {
-  return abi_guard(ctx, [&]() -> int { return opstring_apply_core(ctx, m, dtype, psi_dev, n, terms, n_terms, y_dev, b_re, b_im, dtype_out, out_dev, true); });
-}
-extern "C" int sd_opstring_expect(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_host, const void *ket_host, int64_t n,
-                                  const sd_opterm *terms, int n_terms, double *out) {
-  return abi_guard(ctx, [&]() -> int { return opstring_expect_core(ctx, m, dtype, bra_host, ket_host, n, terms, n_terms, out, false); });
-}
-extern "C" int sd_opstring_expect_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *bra_dev, const void *ket_dev, int64_t n,
-                                      const sd_opterm *terms, int n_terms, double *out) {
-  return abi_guard(ctx, [&]() -> int { return opstring_expect_core(ctx, m, dtype, bra_dev, ket_dev, n, terms, n_terms, out, true); });
 }
 
 extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, const void *r_host, uint64_t seed, int B_kind,
@@ -2651,8 +1916,7 @@ extern "C" int sd_dqt_correlations(sd_ctx *ctx, const sd_model *m, double beta, 
     }
   }
   std::vector<double> h((size_t)(mrow * nt));
-  SD_HIP(ctx, hipMemcpyAsync(h.data(), meas.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  RC(read_back(ctx, h.data(), meas.p, sizeof(double) * h.size()));
   for (int k = 0; k < nt; ++k)
     std::memcpy(num + (size_t)2 * nA * k, h.data() + (size_t)mrow * k, sizeof(double) * 2 * (size_t)nA);
   return SD_OK;
@@ -2790,8 +2054,7 @@ int eigs_core(Op &op, int dtype, int nev, int basis_size, double tol, int64_t ma
         sd_epi_args ea;
         RC(op.apply(dtype, w.p, col(j), SD_EPI_PLAIN, ea));
         RC(cgs_round(j + 1, sc.p, nullptr)); RC(cgs_round(j + 1, sc.p + CO, sc.p + 2 * CO));
-        SD_HIP(ctx, hipMemcpyAsync(hs.data(), sc.p, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RC(read_back(ctx, hs.data(), sc.p, sizeof(double) * hs.size()));
         const int jj = j - c;
         const double alpha = hs[2 * j] + hs[CO + 2 * j];
         beta = std::sqrt(hs[2 * CO]);
@@ -2935,8 +2198,7 @@ extern "C" int sd_block_dots_dev(sd_ctx *ctx, int dtype, const void *V, int64_t 
   const int nc = dtype == SD_C128 ? 2 : 1;
   DBuf o; RC(o.alloc(ctx, 2 * SD_EIGS_BLOCK_COLS));
   RC(sd_k_block_dots(ctx, nc, (const double *)V, ld * nc, ncols, (const double *)w, n, o.p));
-  SD_HIP(ctx, hipMemcpyAsync(out, o.p, sizeof(double) * 2 * (size_t)ncols, hipMemcpyDeviceToHost, ctx->stream));
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  RC(read_back(ctx, out, o.p, sizeof(double) * 2 * (size_t)ncols));
   return SD_OK;
 }); }
 extern "C" int sd_block_axpy_dev(sd_ctx *ctx, int dtype, void *w, const void *V, int64_t ld, int ncols, const double *coef, int64_t n) {
@@ -2975,25 +2237,20 @@ int drive_apply_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi,
   if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
   if (!psi || !out) return sd_set_err(ctx, SD_EARG, "null argument");
   if (on_dev && out == psi) return sd_set_err(ctx, SD_EARG, "out must not alias psi");
-  const int nc = dtype == SD_C128 ? 2 : 1;
-  DBuf in, res;
-  const double *p = (const double *)psi, *yd = (const double *)y;
-  double *o = (double *)out;
-  if (!on_dev) {
-    RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi, nc * n)); p = in.p;
-    RC(res.alloc(ctx, nc * n)); o = res.p;
-    if (y) { RC(h2d(ctx, res.p, y, nc * n)); yd = res.p; }
-  }
+  DevIn in;
+  DevOut o;
+  RC(in.stage(ctx, dtype, psi, on_dev, n));
+  RC(o.open(ctx, out, on_dev, vec_doubles(dtype, n)));
+  const double *yd = (const double *)y;
+  if (!on_dev && y) { RC(h2d(ctx, o.p, y, vec_doubles(dtype, n))); yd = o.p; }     // the host form's y rides in the result block
   if (with_h0) {
     op.use_callback = false;
     op.drive = &tb;
-    RC(op.apply(dtype, o, p, SD_EPI_PLAIN, sd_epi_args()));
+    RC(op.apply(dtype, o.p, in.p, SD_EPI_PLAIN, sd_epi_args()));
   } else {
-    RC(sd_launch_drive_epilogue(ctx, m, dtype, o, yd, p, SD_EPI_PLAIN, sd_epi_args(), tb));
+    RC(sd_launch_drive_epilogue(ctx, m, dtype, o.p, yd, in.p, SD_EPI_PLAIN, sd_epi_args(), tb));
   }
-  if (!on_dev) return d2h(ctx, out, o, nc * n);
-  SD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SD_OK;
+  return o.close(true);                                    // no pool block is in flight: see the table of DESIGN.md 4.5
 }
 
 // psi <- exp(-i tau_s (H0 + sum_k coef[s K + k] D_k)) psi for s = 0 .. n_stages-1 by krylov_evolve_core on the driven operator, the
@@ -3016,14 +2273,11 @@ int driven_evolve_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *ps
     for (int k = 0; k < K; ++k)
       if (!std::isfinite(coef[(size_t)s * K + k])) return sd_set_err(ctx, SD_EARG, "a stage coefficient is not finite");
   }
-  const int nc = dtype == SD_C128 ? 2 : 1;
-  DBuf in, state;
-  const double *src = (const double *)psi0;
-  double *cur = (double *)psit;
-  if (!on_dev) {
-    RC(in.alloc(ctx, nc * n)); RC(h2d(ctx, in.p, psi0, nc * n)); src = in.p;
-    RC(state.alloc(ctx, 2 * n)); cur = state.p;
-  }
+  DevIn in;
+  DevOut state;
+  RC(in.stage(ctx, dtype, psi0, on_dev, n));
+  RC(state.open(ctx, psit, on_dev, 2 * n));
+  double *cur = state.p;
   const int64_t applies0 = ctx->n_applies;
   double min_beta = INFINITY;
   for (int s = 0; s < n_stages; ++s) {
@@ -3032,12 +2286,11 @@ int driven_evolve_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *ps
     for (int k = 0; k < K; ++k) driven = driven || c[k] != 0.0;
     op.drive = nullptr;
     if (driven) { RC(drive_table(ctx, m, drives, K, c, tb)); op.drive = &tb; }
-    RC(krylov_evolve_core(op, s == 0 ? dtype : SD_C128, s == 0 ? src : cur, n, tau[s], kry_m, cur, true, nullptr, &min_beta));
+    RC(krylov_evolve_core(op, s == 0 ? dtype : SD_C128, s == 0 ? in.p : cur, n, tau[s], kry_m, cur, true, nullptr, &min_beta));
     if (info) { info->stages = s + 1; info->applies = ctx->n_applies - applies0; info->min_beta = min_beta; }
   }
   op.drive = nullptr;
-  if (!on_dev) return d2h(ctx, psit, cur, 2 * n);
-  return SD_OK;
+  return state.close(false);                               // krylov_evolve_core has drained the stream
 }
 
 }  // namespace
