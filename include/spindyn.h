@@ -310,6 +310,50 @@ int sd_driven_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0
 int sd_driven_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, const sd_drive *drives, int K,
                          int n_stages, const double *tau, const double *coef, int kry_m, void *psit_out_c128_dev,
                          sd_driven_info *info /* or NULL */);
+/* ---- hopping drives: H(t) = H0 + sum_k c_k(t) O_k with every O_k a diagonal drive or a hopping drive (not in the reference;
+ * DESIGN.md 25) ----
+ * A hopping drive is B = sum_b (z_b S^+_{i[b]} S^-_{j[b]} + conj(z_b) S^-_{i[b]} S^+_{j[b]}), z_b = re[b] + i im[b] (im NULL: real
+ * weights): Hermitian, so the coefficients stay real.  Sites 1-based, i != j, either orientation, a bond may repeat.  For coefficients
+ * c_k the library forms the concatenated list (drive order, then list order, not merged) with weights x_b = c_k re[b], y_b = c_k im[b],
+ * one multiply each, and drops the bonds of a drive whose coefficient is exactly 0.0.  A call is in REAL FORM iff every im of every
+ * hopping drive passed is NULL or exactly zero -- a property of the drives, not of the coefficients.  One gather kernel then forms,
+ * per row with configuration s, acc = (H0 psi)[r] (or y[r], or 0); acc += d(s) psi[r] when the call has a diagonal part (the
+ * arithmetic of the diagonal drives above); and for each bond in list order whose two sites differ in s, with v = psi[partner row]:
+ * real form acc.c += x_b v.c per component; complex form y' = +y_b when site i[b] is up in s and -y_b when site j[b] is (selected),
+ * t = (x_b v.re - y' v.im, x_b v.im + y' v.re), acc += t.  Limits, answered with SD_EARG and a message: K + KH <= SD_DRIVE_MAX, at most
+ * SD_HOP_MAX_BONDS terms in all hopping drives together, sites in 1..L, i != j, finite weights and coefficients, an unsharded model, out
+ * or y sharing memory with psi, and -- in the two apply entries -- an SD_F64 vector with a complex-form list.  SD_EDIM: a wrong length.
+ * sd_hop_drive_check: the limits alone (host only).
+ * sd_hop_apply: out = (sum_k c_k B_k) psi, or that + y when y != NULL (y of psi's dtype; may be out).  out must not alias psi.
+ * sd_driven_hop_apply: out = (H0 + sum_k coef[k] D_k + sum_k coef[K + k] B_k) psi with the built-in H0 (operator level, as
+ *   sd_driven_apply).  out must not alias psi.
+ * sd_driven_hop_evolve: sd_driven_evolve with both kinds of drive: coef[n_stages x (K + KH)], stage s at coef + s (K + KH), the K
+ *   diagonal columns first.  A stage whose hopping coefficients are all exactly zero runs exactly the calls of sd_driven_evolve.  In
+ *   complex form an SD_F64 psi0 is promoted to ComplexF64 once, before the first stage; in real form an SD_F64 first stage stays real.
+ * _dev: the vectors are device pointers; the calls return after the stream has finished. */
+#define SD_HOP_MAX_BONDS 128
+typedef struct sd_hop_drive {
+  int n;
+  const int *i;             /* n entries each (NULL allowed when n == 0) */
+  const int *j;
+  const double *re;
+  const double *im;         /* n entries or NULL */
+} sd_hop_drive;
+int sd_hop_drive_check(const sd_model *m, const sd_hop_drive *hops, int KH);
+int sd_hop_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_hop_drive *hops, int KH,
+                 const double *coef, const void *y_host /* or NULL */, void *out_host);
+int sd_hop_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_hop_drive *hops, int KH,
+                     const double *coef, const void *y_dev /* or NULL */, void *out_dev);
+int sd_driven_hop_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_drive *drives, int K,
+                        const sd_hop_drive *hops, int KH, const double *coef, void *out_host);
+int sd_driven_hop_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_drive *drives, int K,
+                            const sd_hop_drive *hops, int KH, const double *coef, void *out_dev);
+int sd_driven_hop_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, const sd_drive *drives, int K,
+                         const sd_hop_drive *hops, int KH, int n_stages, const double *tau, const double *coef, int kry_m,
+                         void *psit_out_c128_host, sd_driven_info *info /* or NULL */);
+int sd_driven_hop_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, const sd_drive *drives, int K,
+                             const sd_hop_drive *hops, int KH, int n_stages, const double *tau, const double *coef, int kry_m,
+                             void *psit_out_c128_dev, sd_driven_info *info /* or NULL */);
 /* chebyshev_time_evolve   src/TimeEvolution/Chebyshev.jl:61-124  (psi0 ComplexF64) */
 int sd_chebyshev_evolve(sd_ctx *ctx, const sd_model *m, const void *psi0_c128_host, int64_t n, double dt,
                         int cheb_n, double Emin, double Emax, void *psit_out_c128_host);

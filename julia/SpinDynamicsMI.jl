@@ -23,6 +23,7 @@ export Model, build_model, XXZChain, momenta, apply_H!, apply_rescaled_H!, Sz_q_
        site_project, kpm_site_moments, kpm_reconstruct_signed, kpm_correlation_matrix, kpm_sqw_sites,
        chebyshev_imag_coeffs, chebyshev_terms, thermal_state, spin_current, current_expectation, energy_current_terms, energy_current, energy_current_expectation, pair_correlations, bond_operator, dimer_correlations, symmetry_code, is_symmetric, symmetry_apply, translate, reflect, spin_flip, symmetry_overlaps, momentum_weights, symmetry_combine, symmetry_project, OpTerm, op_string, operator_adjoint, operator_check, hamiltonian_terms, operator_apply, operator_expectations, string_order, basis_moments, participation_entropy, counting_range, counting_statistics, number_entropy, CutBlock, cut_blocks, cut_gram, permute_sites, site_permute_sources, subsystem_permutation, subsystem_gram, sample_uniforms, sample_configurations, typicality_sample, typicality_correlation_function,
        DiagonalDrive, field_drive, gradient_drive, zz_drive, drive_check, diagonal_apply, driven_apply, magnus_schedule, piecewise_schedule, stage_evolve, driven_time_evolve,
+       HoppingDrive, exchange_drive, current_drive, hop_drive_check, hopping_apply,
        magnetization_per_site, connected_correlations, structure_factor_Sq,
        domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 
@@ -1151,6 +1152,96 @@ function driven_time_evolve(model::Model, ψ0::AbstractVector, drives::Vector{Di
         measure === nothing || push!(results, measure(t0 + done * dt, ψ))
     end
     return ψ, results
+end
+
+# ---- hopping drives: B = Σ_b (z_b S⁺_i S⁻_j + conj(z_b) S⁻_i S⁺_j) beside the diagonal ones (include/spindyn.h, "hopping drives";
+# DESIGN.md 25) ----
+# bonds[b] = (i, j), sites 1-based, i ≠ j in either orientation; complex weights.  Real weights travel without an im list, so a call
+# whose hopping drives are all real runs in real form.
+struct HoppingDrive
+    hi::Vector{Cint}
+    hj::Vector{Cint}
+    re::Vector{Float64}
+    im::Union{Nothing,Vector{Float64}}
+end
+function HoppingDrive(bonds, weights=nothing)
+    w = weights === nothing ? ones(ComplexF64, length(bonds)) : Vector{ComplexF64}(weights)
+    length(w) == length(bonds) || throw(ArgumentError("weights needs one entry per bond"))
+    return HoppingDrive(Cint[b[1] for b in bonds], Cint[b[2] for b in bonds], real.(w), all(iszero, imag.(w)) ? nothing : imag.(w))
+end
+# the model's own hop bonds with their own amplitudes: f(t) is the relative modulation δJ/J
+exchange_drive(model::Model) = HoppingDrive([(b[1], b[2]) for b in model.hopping_list], [b[3] for b in model.hopping_list])
+# z_b = i w_b t_b: the operator of spin_current
+current_drive(model::Model; weights=nothing) =
+    HoppingDrive([(b[1], b[2]) for b in model.hopping_list],
+                 [im * (weights === nothing ? 1.0 : weights[k]) * b[3] for (k, b) in enumerate(model.hopping_list)])
+
+struct CHopDrive             # sd_hop_drive
+    n::Cint
+    i::Ptr{Cint}
+    j::Ptr{Cint}
+    re::Ptr{Float64}
+    im::Ptr{Float64}
+end
+# the sd_hop_drive array of a list; the pointers are into the drives' own arrays: keep `hops` alive (GC.@preserve) while it is in use
+pack_hops(hops::Vector{HoppingDrive}) =
+    CHopDrive[CHopDrive(length(d.hi), pointer(d.hi), pointer(d.hj), pointer(d.re), d.im === nothing ? Ptr{Float64}(C_NULL) : pointer(d.im))
+              for d in hops]
+
+function hop_drive_check(model::Model, hops::Vector{HoppingDrive})
+    GC.@preserve hops begin
+        arr = pack_hops(hops)
+        check(ccall((:sd_hop_drive_check, libspindyn), Cint, (Ptr{Cvoid}, Ptr{CHopDrive}, Cint), model.h, arr, length(arr)), model.ctx.h)
+    end
+    return nothing
+end
+
+# (Σ_k coefs[k] B_k) ψ, plus y when given; a list with complex weights needs a ComplexF64 ψ
+function hopping_apply(ψ::Vector{T}, model::Model, hops::Vector{HoppingDrive}, coefs::AbstractVector;
+                       y::Union{Nothing,Vector{T}}=nothing) where {T<:Union{Float64,ComplexF64}}
+    out = similar(ψ)
+    c = Vector{Float64}(coefs)
+    GC.@preserve hops begin
+        arr = pack_hops(hops)
+        check(ccall((:sd_hop_apply, libspindyn), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{CHopDrive}, Cint, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+                    model.ctx.h, model.h, dtype_code(T), ψ, length(ψ), arr, length(arr), c, y === nothing ? C_NULL : y, out), model.ctx.h)
+    end
+    return out
+end
+
+# out = (H0 + Σ_k coefs[k] D_k + Σ_k coefs[K + k] B_k) ψ: the diagonal drives' coefficients first
+function driven_apply(out::Vector{T}, ψ::Vector{T}, model::Model, drives::Vector{DiagonalDrive}, hops::Vector{HoppingDrive},
+                      coefs::AbstractVector) where {T<:Union{Float64,ComplexF64}}
+    c = Vector{Float64}(coefs)
+    length(c) == length(drives) + length(hops) || throw(ArgumentError("coefs needs one entry per drive, the diagonal ones first"))
+    GC.@preserve drives hops begin
+        arr = pack_drives(model, drives)
+        harr = pack_hops(hops)
+        check(ccall((:sd_driven_hop_apply, libspindyn), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{CDrive}, Cint, Ptr{CHopDrive}, Cint, Ptr{Float64}, Ptr{Cvoid}),
+                    model.ctx.h, model.h, dtype_code(T), ψ, length(ψ), arr, length(arr), harr, length(harr), c, out), model.ctx.h)
+    end
+    return out
+end
+
+# stage_evolve with both kinds of drive: coef is (K + KH) x stages, the rows of the diagonal drives first -> (ψ, info)
+function stage_evolve(model::Model, ψ0::AbstractVector, drives::Vector{DiagonalDrive}, hops::Vector{HoppingDrive}, tau::Vector{Float64},
+                      coef::Matrix{Float64}; kry_m::Int=30)
+    x = eltype(ψ0) <: Complex ? Vector{ComplexF64}(ψ0) : Vector{Float64}(ψ0)
+    size(coef) == (length(drives) + length(hops), length(tau)) || throw(ArgumentError("coef must be (K + KH) x stages"))
+    out = Vector{ComplexF64}(undef, length(x))
+    info = DrivenInfo()
+    GC.@preserve drives hops begin
+        arr = pack_drives(model, drives)
+        harr = pack_hops(hops)
+        check(ccall((:sd_driven_hop_evolve, libspindyn), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{CDrive}, Cint, Ptr{CHopDrive}, Cint, Cint, Ptr{Float64}, Ptr{Float64},
+                     Cint, Ptr{Cvoid}, Ref{DrivenInfo}),
+                    model.ctx.h, model.h, dtype_code(eltype(x)), x, length(x), arr, length(arr), harr, length(harr), length(tau), tau, coef,
+                    kry_m, out, info), model.ctx.h)
+    end
+    return out, (stages=Int(info.stages), applies=info.applies, min_beta=info.min_beta)
 end
 
 end # module

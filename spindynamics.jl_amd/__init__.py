@@ -37,9 +37,10 @@ from .entanglement import (CutBlock, cut_blocks, cut_gram, cut_plan_info, dense_
                            mutual_information, partial_transpose, reduced_density_matrix, schmidt_gap, spectrum_from_blocks,
                            subsystem_density_matrix, subsystem_entropy, subsystem_gram, subsystem_spectrum,
                            symmetry_resolved_entanglement, symmetry_resolved_from_spectrum, two_site_density_matrix)
-from .driven import (DiagonalDrive, diagonal_apply, diagonal_expectation, drive_check, driven_apply, driven_time_evolve,
-                     field_drive, gradient_drive, instantaneous_energy, magnus_schedule, piecewise_schedule, stage_evolve,
-                     zz_drive)
+from .driven import (DiagonalDrive, HoppingDrive, current_drive, diagonal_apply, diagonal_expectation, drive_check,
+                     drive_expectation, driven_apply, driven_time_evolve, exchange_drive, field_drive, gradient_drive,
+                     hopping_apply, instantaneous_energy, magnus_schedule, peierls_drives, peierls_functions,
+                     piecewise_schedule, stage_evolve, zz_drive)
 from . import initial_states
 from .initial_states import domain_wall_state, neel_state, polarized_state, polarized_state_with_flips
 from .api import dynamical_structure_factor, groundstate, structure_factor, time_evolve

@@ -89,6 +89,12 @@ class sd_driven_info(C.Structure):
     _fields_ = [("stages", C.c_int), ("applies", C.c_int64), ("min_beta", C.c_double)]
 
 
+class sd_hop_drive(C.Structure):
+    """one hopping drive (include/spindyn.h): n bonds (i, j) with weights re + i im (im NULL: real), sites 1-based"""
+    _fields_ = [("n", C.c_int), ("i", C.POINTER(C.c_int)), ("j", C.POINTER(C.c_int)), ("re", C.POINTER(C.c_double)),
+                ("im", C.POINTER(C.c_double))]
+
+
 class sd_comm_callbacks(C.Structure):
     _fields_ = [("user", C.c_void_p), ("exchange_start", EXCHANGE_START_FN), ("exchange_wait", EXCHANGE_WAIT_FN),
                 ("allreduce_sum", ALLREDUCE_FN)]
@@ -148,6 +154,15 @@ PROTOTYPES = {
     "sd_driven_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, _dp, _vp]),
     "sd_driven_evolve": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, _i, _dp, _dp, _i, _vp, C.POINTER(sd_driven_info)]),
     "sd_driven_evolve_dev": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, _i, _dp, _dp, _i, _vp, C.POINTER(sd_driven_info)]),
+    "sd_hop_drive_check": (_i, [_vp, C.POINTER(sd_hop_drive), _i]),
+    "sd_hop_apply": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_hop_drive), _i, _dp, _vp, _vp]),
+    "sd_hop_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_hop_drive), _i, _dp, _vp, _vp]),
+    "sd_driven_hop_apply": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, C.POINTER(sd_hop_drive), _i, _dp, _vp]),
+    "sd_driven_hop_apply_dev": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, C.POINTER(sd_hop_drive), _i, _dp, _vp]),
+    "sd_driven_hop_evolve": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, C.POINTER(sd_hop_drive), _i, _i, _dp, _dp, _i, _vp,
+                                  C.POINTER(sd_driven_info)]),
+    "sd_driven_hop_evolve_dev": (_i, [_vp, _vp, _i, _vp, _i64, C.POINTER(sd_drive), _i, C.POINTER(sd_hop_drive), _i, _i, _dp, _dp, _i, _vp,
+                                      C.POINTER(sd_driven_info)]),
     "sd_chebyshev_evolve": (_i, [_vp, _vp, _vp, _i64, _d, _i, _d, _d, _vp]),
     "sd_chebyshev_evolve_dev": (_i, [_vp, _vp, _vp, _i64, _d, _i, _d, _d, _vp]),
     "sd_kpm_moments": (_i, [_vp, _vp, _vp, _i64, _i, _d, _d, _dp]),

@@ -1122,3 +1122,65 @@ extern "C" int sd_drive_check(const sd_model *m, const sd_drive *drives, int K) 
     return rc ? sd_set_err(m->ctx, rc, "sd_drive_check: " + err) : SD_OK;
   });
 }
+
+// ---- hopping drives: the limits of a hopping-drive list, its form, and the effective list of one stage ----
+// coef == null: the limits and the form alone (out.n = the terms of all drives, nothing else written).  coef: KH coefficients.
+int sd_hop_build(const sd_model *m, const sd_hop_drive *hops, int KH, int K_diag, const double *coef, sd_hop_table &out, std::string &err) {
+  if (!m) { err = "null model"; return SD_EARG; }
+  if (KH < 0 || K_diag < 0 || KH > SD_DRIVE_MAX - K_diag) {
+    err = "diagonal and hopping drives together must be 0.." + std::to_string(SD_DRIVE_MAX);
+    return SD_EARG;
+  }
+  if (KH > 0 && !hops) { err = "null hopping-drive list"; return SD_EARG; }
+  if (m->L < 1 || m->L > SD_MAX_L) { err = "hopping drives need 1 <= L <= 63"; return SD_EARG; }
+  if (m->nranks != 1) { err = "hopping drives need an unsharded model"; return SD_EARG; }
+  const int L = m->L;
+  int nb = 0;
+  bool cplx = false;
+  for (int k = 0; k < KH; ++k) {
+    const sd_hop_drive &d = hops[k];
+    const std::string who = "hopping drive " + std::to_string(k);
+    if (coef && !std::isfinite(coef[k])) { err = who + ": the coefficient is not finite"; return SD_EARG; }
+    if (d.n < 0) { err = who + ": negative bond count"; return SD_EARG; }
+    if (d.n > 0 && (!d.i || !d.j || !d.re)) { err = who + ": null bond list"; return SD_EARG; }
+    if (d.n > SD_HOP_MAX_BONDS - nb) {
+      err = "more than " + std::to_string(SD_HOP_MAX_BONDS) + " hop terms in the drives together";
+      return SD_EARG;
+    }
+    for (int b = 0; b < d.n; ++b) {
+      const int i = d.i[b], j = d.j[b];
+      if (i < 1 || i > L || j < 1 || j > L) { err = who + ": a bond site is outside 1..L"; return SD_EARG; }
+      if (i == j) { err = who + ": the two sites of a bond must differ"; return SD_EARG; }
+      if (!std::isfinite(d.re[b]) || (d.im && !std::isfinite(d.im[b]))) { err = who + ": a bond weight is not finite"; return SD_EARG; }
+      if (d.im && d.im[b] != 0.0) cplx = true;
+    }
+    nb += d.n;
+  }
+  out.complex_form = cplx ? 1 : 0;
+  out.n = nb;
+  if (!coef) return SD_OK;
+  int at = 0;
+  for (int k = 0; k < KH; ++k) {
+    if (coef[k] == 0.0) continue;                            // a switched-off drive gathers nothing
+    const sd_hop_drive &d = hops[k];
+    for (int b = 0; b < d.n; ++b, ++at) {
+      const int bi = d.i[b] - 1, bj = d.j[b] - 1;
+      const int lo = bi < bj ? bi : bj, hi = bi < bj ? bj : bi;
+      out.bits[at] = (uint32_t)(lo | (hi << 8) | ((bi > bj ? 1 : 0) << 16));
+      out.xy[2 * at] = coef[k] * d.re[b];
+      out.xy[2 * at + 1] = d.im ? coef[k] * d.im[b] : 0.0;
+    }
+  }
+  out.n = at;
+  return SD_OK;
+}
+
+extern "C" int sd_hop_drive_check(const sd_model *m, const sd_hop_drive *hops, int KH) {
+  if (!m) return SD_EARG;
+  return abi_guard(m->ctx, [&]() -> int {
+    std::string err;
+    sd_hop_table none;
+    const int rc = sd_hop_build(m, hops, KH, 0, nullptr, none, err);
+    return rc ? sd_set_err(m->ctx, rc, "sd_hop_drive_check: " + err) : SD_OK;
+  });
+}

@@ -48,6 +48,13 @@ int plain_op(sd_ctx *ctx, const sd_model *m, int dtype, double *out, const doubl
 // What a recursion needs from "the operator": the apply on this rank's rows (halo exchange included) and the sum of device
 // scalars over the ranks.  Unsharded (comm == nullptr, nranks == 1) both reduce to the plain launch / nothing, so the same
 // loops serve the single-GPU and the sharded entry points.
+// the effective hopping list of one stage on the device (kernels_hop_drive.hip)
+struct HopDev {
+  int n = 0, complex_form = 0;
+  const uint32_t *bits = nullptr;
+  const double *xy = nullptr;
+};
+
 struct Op {
   sd_ctx *ctx = nullptr;
   const sd_model *m = nullptr;
@@ -58,6 +65,7 @@ struct Op {
   bool use_callback = true;  // false: always the built-in operator (the operator-level entry sd_apply_sharded, which a caller's
                              // operator may itself call on a sharded model: include/spindyn.h, sd_ctx_set_apply_callback)
   const sd_drive_table *drive = nullptr;   // a diagonal drive on top of the operator (driven_evolve_core), or null
+  const HopDev *hop = nullptr;             // a hopping drive on top of the operator (driven_hop_evolve_core), or null
 
   int init(sd_ctx *c, const sd_model *mm, sd_comm *cm) {
     if (!c) return SD_EARG;
@@ -76,7 +84,7 @@ struct Op {
   // out = epilogue(H psi) on the owned rows.  Sharded: pack (cell mode), post the exchange, interior tiles, wait, boundary tiles.
   int apply(int dtype, double *out, const double *psi, int epi, sd_epi_args ea) {
     ++ctx->n_applies;
-    if (drive) return apply_driven(dtype, out, psi, epi, ea);
+    if (drive || hop) return apply_driven(dtype, out, psi, epi, ea);
     if (use_callback && ctx->user_apply) return user_op(ctx, dtype, out, psi, n, epi, ea);
     if (m->nranks == 1) return sd_launch_apply(ctx, m, dtype, out, psi, epi, ea, 0);
     ea.halo = halo.p;
@@ -92,15 +100,17 @@ struct Op {
     return sd_launch_apply(ctx, m, dtype, out, psi, epi, ea, 0);
   }
   // out = epilogue((H0 + D) psi): H0 psi into out by the caller's operator or the built-in apply, then the drive pass with the
-  // recursion's epilogue over out in place (kernels_drive.hip).  Unsharded models.
+  // recursion's epilogue over out in place (kernels_drive.hip; with a hop table kernels_hop_drive.hip, which adds B psi in the same
+  // pass).  Unsharded models.
   int apply_driven(int dtype, double *out, const double *psi, int epi, const sd_epi_args &ea) {
-    if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, "diagonal drives need an unsharded model");
+    if (m->nranks != 1) return sd_set_err(ctx, SD_EARG, hop ? "hopping drives need an unsharded model" : "diagonal drives need an unsharded model");
     if (use_callback && ctx->user_apply) {
       if (ctx->user_apply(ctx->user_apply_data, dtype, out, psi, n, (void *)ctx->stream))
         return sd_set_err(ctx, SD_ECOMM, "the apply callback returned an error");
     } else {
       RC(sd_launch_apply(ctx, m, dtype, out, psi, SD_EPI_PLAIN, sd_epi_args(), 0));
     }
+    if (hop) return sd_launch_hop_drive_epilogue(ctx, m, dtype, out, out, psi, epi, ea, drive, hop->n, hop->complex_form, hop->bits, hop->xy);
     return sd_launch_drive_epilogue(ctx, m, dtype, out, out, psi, epi, ea, *drive);
   }
   // device scalars <- their sum over the ranks (in place, ordered on the context's stream)
@@ -140,11 +150,11 @@ int peek_breakdown(sd_ctx *ctx, const double *d_be, int count, double tol, std::
 // built-in operator on an unsharded tiled plan of at most 16384 tiles, vectors of at most 2^22 rows (launch-bound sizes).
 bool launches_shareable(const Op &op) {
   const sd_model *m = op.m;
-  return op.ctx->q_batch && m->nranks == 1 && !op.ctx->user_apply && !op.drive && m->p >= 0 && m->dm.n_singles <= 16384 && op.n <= ((int64_t)1 << 22);
+  return op.ctx->q_batch && m->nranks == 1 && !op.ctx->user_apply && !op.drive && !op.hop && m->p >= 0 && m->dm.n_singles <= 16384 && op.n <= ((int64_t)1 << 22);
 }
 bool lanczos_fused_ok(const Op &op, int Qb) {
   const sd_model *m = op.m;
-  return m->nranks == 1 && !op.ctx->user_apply && !op.drive && m->p >= 0 && m->dm.n_singles <= 4096 && op.n <= ((int64_t)1 << 22) &&
+  return m->nranks == 1 && !op.ctx->user_apply && !op.drive && !op.hop && m->p >= 0 && m->dm.n_singles <= 4096 && op.n <= ((int64_t)1 << 22) &&
          (int64_t)Qb * op.n * 16 * 3 <= ((int64_t)4 << 30);
 }
 int lanczos_fused(Op &op, int Qb, double *u0, int mm, int form, int negate, double tol, std::vector<double> &alpha,
@@ -2293,7 +2303,164 @@ int driven_evolve_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *ps
   return state.close(false);                               // krylov_evolve_core has drained the stream
 }
 
+// ---- hopping drives on top: H(t) = H0 + sum_k c_k(t) O_k, every O_k diagonal or a hopping drive ----
+
+int hop_table(sd_ctx *ctx, const sd_model *m, const sd_hop_drive *hops, int KH, int K, const double *coef, sd_hop_table &ht) {
+  std::string err;
+  const int rc = sd_hop_build(m, hops, KH, K, coef, ht, err);
+  return rc ? sd_set_err(ctx, rc, err) : SD_OK;
+}
+
+// The device slot of a call's hop table, one block of the context's pool: SD_HOP_MAX_BONDS site words, then as many (x, y) pairs.
+// The words go up when the set of switched-on drives changes (once per call unless a coefficient passes through exactly zero), the
+// weights with every table.  Every user of the slot drains the stream before the next upload and before the block goes back.
+struct HopSlot {
+  DBuf buf;
+  HopDev dev;
+  uint32_t words_of = ~0u;                                 // the switched-on drives whose words are on the device
+  int upload(sd_ctx *ctx, const sd_hop_table &ht, int KH, const double *coef) {
+    if (!buf.p) {
+      RC(buf.alloc_bytes(ctx, SD_HOP_MAX_BONDS * (sizeof(uint32_t) + 2 * sizeof(double))));
+      dev.bits = (const uint32_t *)buf.p;
+      dev.xy = (const double *)((const char *)buf.p + SD_HOP_MAX_BONDS * sizeof(uint32_t));
+    }
+    uint32_t on = 0;
+    for (int k = 0; k < KH; ++k) on |= (coef[k] != 0.0 ? 1u : 0u) << k;
+    dev.n = ht.n;
+    dev.complex_form = ht.complex_form;
+    if (ht.n == 0) return SD_OK;
+    if (on != words_of) { RC(sd_xfer_h2d(ctx, (void *)dev.bits, ht.bits, sizeof(uint32_t) * (size_t)ht.n)); words_of = on; }
+    return sd_xfer_h2d(ctx, (void *)dev.xy, ht.xy, 2 * sizeof(double) * (size_t)ht.n);
+  }
+};
+
+// with_h0: out = (H0 + sum_k coef[k] D_k + sum_k coef[K + k] B_k) psi with the built-in H0 (operator level); else K == 0 and
+// out = (sum_k coef[k] B_k) psi (+ y).  A list without a term in effect runs drive_apply_core's calls.
+int hop_apply_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi, int64_t n, const sd_drive *drives, int K,
+                   const sd_hop_drive *hops, int KH, const double *coef, const void *y, void *out, bool with_h0, bool on_dev) {
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "dtype must be SD_F64 or SD_C128");
+  if (K < 0 || KH < 0) return sd_set_err(ctx, SD_EARG, "negative drive count");
+  if (K + KH > 0 && !coef) return sd_set_err(ctx, SD_EARG, "null coefficients");
+  sd_drive_table tb;
+  sd_hop_table ht;
+  const double none = 0.0;
+  RC(drive_table(ctx, m, drives, K, K > 0 ? coef : &none, tb));
+  RC(hop_table(ctx, m, hops, KH, K, KH > 0 ? coef + K : nullptr, ht));
+  if (KH == 0) ht.n = 0;
+  if (ht.complex_form && dtype != SD_C128)
+    return sd_set_err(ctx, SD_EARG, "a hopping drive with complex weights needs a ComplexF64 vector");
+  if (n != m->N) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (!psi || !out) return sd_set_err(ctx, SD_EARG, "null argument");
+  const size_t bytes = sizeof(double) * (size_t)vec_doubles(dtype, n);
+  if (on_dev && (ranges_overlap(out, bytes, psi, bytes) || (y && ranges_overlap(y, bytes, psi, bytes))))
+    return sd_set_err(ctx, SD_EARG, "out and y must not share memory with psi");
+  if (ht.n == 0 && with_h0) return drive_apply_core(ctx, m, dtype, psi, n, drives, K, coef, nullptr, out, true, on_dev);
+  HopSlot slot;
+  RC(slot.upload(ctx, ht, KH, coef ? coef + K : nullptr));
+  DevIn in;
+  DevOut o;
+  RC(in.stage(ctx, dtype, psi, on_dev, n));
+  RC(o.open(ctx, out, on_dev, vec_doubles(dtype, n)));
+  const double *yd = (const double *)y;
+  if (!on_dev && y) { RC(h2d(ctx, o.p, y, vec_doubles(dtype, n))); yd = o.p; }     // the host form's y rides in the result block
+  if (with_h0) {
+    op.use_callback = false;
+    op.drive = K > 0 ? &tb : nullptr;
+    op.hop = &slot.dev;
+    RC(op.apply(dtype, o.p, in.p, SD_EPI_PLAIN, sd_epi_args()));
+  } else {
+    RC(sd_launch_hop_drive_epilogue(ctx, m, dtype, o.p, yd, in.p, SD_EPI_PLAIN, sd_epi_args(), nullptr, slot.dev.n, slot.dev.complex_form,
+                                    slot.dev.bits, slot.dev.xy));
+  }
+  return o.close(true);                                    // the slot goes back to the pool: nothing may still read it
+}
+
+// driven_evolve_core with hopping drives: coef[n_stages x (K + KH)], the diagonal columns first.  A stage without a hop term in
+// effect runs driven_evolve_core's calls.  Complex form: an SD_F64 psi0 is promoted once, before the first stage.
+int driven_hop_evolve_core(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0, int64_t n, const sd_drive *drives, int K,
+                           const sd_hop_drive *hops, int KH, int n_stages, const double *tau, const double *coef, int kry_m, void *psit,
+                           bool on_dev, sd_driven_info *info) {
+  if (KH == 0) return driven_evolve_core(ctx, m, dtype, psi0, n, drives, K, n_stages, tau, coef, kry_m, psit, on_dev, info);
+  Op op; RC(op.init(ctx, m, nullptr));
+  if (info) { info->stages = 0; info->applies = 0; info->min_beta = INFINITY; }
+  if (!psi0 || !psit) return sd_set_err(ctx, SD_EARG, "null vector");
+  if (n_stages < 1 || !tau) return sd_set_err(ctx, SD_EARG, "a driven evolution needs at least one stage and its durations");
+  if (K < 0 || KH < 0) return sd_set_err(ctx, SD_EARG, "negative drive count");
+  if (!coef) return sd_set_err(ctx, SD_EARG, "null coefficients");
+  if (dtype != SD_F64 && dtype != SD_C128) return sd_set_err(ctx, SD_EARG, "bad dtype");
+  if (n != op.n) return sd_set_err(ctx, SD_EDIM, "vector length does not match the basis dimension");
+  if (kry_m < 1) return sd_set_err(ctx, SD_EARG, "kry_m must be >= 1");
+  sd_drive_table tb;
+  sd_hop_table ht;
+  RC(drive_table(ctx, m, drives, K, nullptr, tb));                       // the limits, before anything runs
+  RC(hop_table(ctx, m, hops, KH, K, nullptr, ht));
+  const bool complex_form = ht.complex_form != 0;
+  const int KT = K + KH;
+  for (int s = 0; s < n_stages; ++s) {
+    if (!std::isfinite(tau[s])) return sd_set_err(ctx, SD_EARG, "a stage duration is not finite");
+    for (int k = 0; k < KT; ++k)
+      if (!std::isfinite(coef[(size_t)s * KT + k])) return sd_set_err(ctx, SD_EARG, "a stage coefficient is not finite");
+  }
+  DevIn in;
+  DevOut state;
+  HopSlot slot;
+  RC(in.stage(ctx, dtype, psi0, on_dev, n));
+  RC(state.open(ctx, psit, on_dev, 2 * n));
+  double *cur = state.p;
+  bool started = false;                                                  // cur holds the state (ComplexF64)
+  if (complex_form && dtype == SD_F64) { RC(sd_k_promote(ctx, cur, in.p, 1, n)); started = true; }
+  const int64_t applies0 = ctx->n_applies;
+  double min_beta = INFINITY;
+  for (int s = 0; s < n_stages; ++s) {
+    const double *c = coef + (size_t)s * KT;
+    bool driven = false;
+    for (int k = 0; k < K; ++k) driven = driven || c[k] != 0.0;
+    op.drive = nullptr;
+    op.hop = nullptr;
+    if (driven) { RC(drive_table(ctx, m, drives, K, c, tb)); op.drive = &tb; }
+    RC(hop_table(ctx, m, hops, KH, K, c + K, ht));
+    if (ht.n > 0) { RC(slot.upload(ctx, ht, KH, c + K)); op.hop = &slot.dev; }
+    RC(krylov_evolve_core(op, started ? SD_C128 : dtype, started ? cur : in.p, n, tau[s], kry_m, cur, true, nullptr, &min_beta));
+    started = true;
+    if (info) { info->stages = s + 1; info->applies = ctx->n_applies - applies0; info->min_beta = min_beta; }
+  }
+  op.drive = nullptr;
+  op.hop = nullptr;
+  return state.close(false);                               // krylov_evolve_core has drained the stream
+}
+
 }  // namespace
+
+extern "C" int sd_hop_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_hop_drive *hops, int KH,
+                            const double *coef, const void *y_host, void *out_host) { return abi_guard(ctx, [&]() -> int {
+  return hop_apply_core(ctx, m, dtype, psi_host, n, nullptr, 0, hops, KH, coef, y_host, out_host, false, false);
+}); }
+extern "C" int sd_hop_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_hop_drive *hops, int KH,
+                                const double *coef, const void *y_dev, void *out_dev) { return abi_guard(ctx, [&]() -> int {
+  return hop_apply_core(ctx, m, dtype, psi_dev, n, nullptr, 0, hops, KH, coef, y_dev, out_dev, false, true);
+}); }
+extern "C" int sd_driven_hop_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_drive *drives,
+                                   int K, const sd_hop_drive *hops, int KH, const double *coef, void *out_host) {
+  return abi_guard(ctx, [&]() -> int {
+  return hop_apply_core(ctx, m, dtype, psi_host, n, drives, K, hops, KH, coef, nullptr, out_host, true, false);
+}); }
+extern "C" int sd_driven_hop_apply_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_dev, int64_t n, const sd_drive *drives,
+                                       int K, const sd_hop_drive *hops, int KH, const double *coef, void *out_dev) {
+  return abi_guard(ctx, [&]() -> int {
+  return hop_apply_core(ctx, m, dtype, psi_dev, n, drives, K, hops, KH, coef, nullptr, out_dev, true, true);
+}); }
+extern "C" int sd_driven_hop_evolve(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_host, int64_t n, const sd_drive *drives,
+                                    int K, const sd_hop_drive *hops, int KH, int n_stages, const double *tau, const double *coef,
+                                    int kry_m, void *psit_host, sd_driven_info *info) { return abi_guard(ctx, [&]() -> int {
+  return driven_hop_evolve_core(ctx, m, dtype, psi0_host, n, drives, K, hops, KH, n_stages, tau, coef, kry_m, psit_host, false, info);
+}); }
+extern "C" int sd_driven_hop_evolve_dev(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi0_dev, int64_t n, const sd_drive *drives,
+                                        int K, const sd_hop_drive *hops, int KH, int n_stages, const double *tau, const double *coef,
+                                        int kry_m, void *psit_dev, sd_driven_info *info) { return abi_guard(ctx, [&]() -> int {
+  return driven_hop_evolve_core(ctx, m, dtype, psi0_dev, n, drives, K, hops, KH, n_stages, tau, coef, kry_m, psit_dev, true, info);
+}); }
+
 
 extern "C" int sd_diag_apply(sd_ctx *ctx, const sd_model *m, int dtype, const void *psi_host, int64_t n, const sd_drive *drives, int K,
                              const double *coef, const void *y_host, void *out_host) { return abi_guard(ctx, [&]() -> int {

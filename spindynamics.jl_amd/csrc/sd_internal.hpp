@@ -492,6 +492,28 @@ int sd_drive_build(const sd_model *m, const sd_drive *drives, int K, const doubl
 int sd_launch_drive_epilogue(sd_ctx *ctx, const sd_model *m, int dtype, void *out, const void *h, const void *psi, int epi,
                              const sd_epi_args &ea, const sd_drive_table &table);
 
+// Hopping drives (kernels_hop_drive.hip): B = sum_b (z_b S^+_{i_b} S^-_{j_b} + conj(z_b) S^-_{i_b} S^+_{j_b}), the
+// effective hopping operator of one stage.  The host table of sd_hop_build: the concatenated list (drive order, then list order, not
+// merged, the bonds of a drive whose coefficient is exactly 0.0 dropped) with weights (x, y) = (c_k re_b, c_k im_b), one multiply each.
+struct sd_hop_table {
+  int n = 0;                              // terms in effect (<= SD_HOP_MAX_BONDS)
+  int complex_form = 0;                   // some im of some drive passed is non-zero: a property of the drives, not of the coefficients
+  uint32_t bits[SD_HOP_MAX_BONDS];        // lo | hi << 8 | (site i is the higher bit) << 16, 0-based bits lo < hi (sd_dgroup::bits)
+  double xy[2 * SD_HOP_MAX_BONDS];        // (x_b, y_b)
+};
+// coef == null: the limits and the form alone (n = the terms of all drives).  SD_EARG with a message in `err`: see sd_hop_drive_check.
+// K_diag: the diagonal drives of the same call (K_diag + KH <= SD_DRIVE_MAX).
+int sd_hop_build(const sd_model *m, const sd_hop_drive *hops, int KH, int K_diag, const double *coef, sd_hop_table &out, std::string &err);
+// bits_dev / xy_dev: the n_hop site words and (x, y) pairs of such a table in device memory (recur.cpp keeps them in one block of the
+// context's pool for the call).
+// out[r] = epilogue(h[r] + d(s_r) psi[r] + (B psi)[r]) on the rows of an unsharded model with device tables: the step of a recursion on
+// H0 + D + B given h = H0 psi.  diag == null: no diagonal part.  out may alias h; psi must alias neither.  NC = 1 needs the real form.
+// h == null: h = 0.  The sums of a DOT / KPM / RESCALE_DOT epilogue are reduced as sd_launch_drive_epilogue reduces them.  Queued on
+// the context's stream, deterministic.
+int sd_launch_hop_drive_epilogue(sd_ctx *ctx, const sd_model *m, int dtype, void *out, const void *h, const void *psi, int epi,
+                                 const sd_epi_args &ea, const sd_drive_table *diag, int n_hop, int complex_form,
+                                 const uint32_t *bits_dev, const double *xy_dev);
+
 // BLAS-1 style kernels on device vectors of `n` doubles (n = nc * N).
 // Reductions write their result to ctx->d_scalars[slot..] (device memory) in a
 // fixed, deterministic order; sd_read_scalars copies them to the host.

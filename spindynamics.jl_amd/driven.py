@@ -8,6 +8,15 @@ commutator-free Magnus scheme (magnus_schedule), or the protocol itself where it
 every stage is one Krylov propagation on H0 + sum_k c_k D_k (sd_driven_evolve): the built-in apply followed by one elementwise
 kernel that adds d(s) psi and runs the Lanczos step's epilogue, with the state on the device from the first stage to the last.
 
+Hopping drives sit beside the diagonal ones:
+
+    B_k = sum_b (z_{k,b} S^+_{i_b} S^-_{j_b} + conj(z_{k,b}) S^-_{i_b} S^+_{j_b})
+
+(modulated exchange, bond-selective quenches, and -- as the pair T_delta, J_delta of peierls_drives -- the Peierls phase of a vector
+potential).  B_k is Hermitian, so the coefficient functions stay real.  drive_check, driven_apply, stage_evolve, driven_time_evolve
+and instantaneous_energy take lists that mix both kinds in any order (sd_driven_hop_evolve: one gather kernel adds d(s) psi and
+B psi to H0 psi and runs the Lanczos step's epilogue); a list without a HoppingDrive makes exactly the library calls it made before.
+
 Sites are 1-based, as in build_model.  Vectors are numpy arrays or torch CUDA tensors, as everywhere in the package.
 """
 import ctypes as C
@@ -24,6 +33,7 @@ _ip = C.POINTER(C.c_int)
 
 MAX_DRIVES = 16        # SD_DRIVE_MAX
 MAX_DRIVE_BONDS = 128  # SD_DRIVE_MAX_BONDS, all drives of a call together
+MAX_HOP_BONDS = 128    # SD_HOP_MAX_BONDS, all hopping drives of a call together
 
 
 class DiagonalDrive:
@@ -70,6 +80,144 @@ def zz_drive(model, bonds=None, weights=None):
     return DiagonalDrive(bonds=bonds, bond_weights=weights)
 
 
+class HoppingDrive:
+    """B = sum_b (weights[b] S^+_i S^-_j + conj(weights[b]) S^-_i S^+_j) over bonds[b] = (i, j), sites 1-based, i != j in either
+    orientation; weights complex (ones by default).  A bond may repeat (its terms are added one after the other, not merged).  A
+    drive whose weights are all real is passed to the library without imaginary parts: a call whose hopping drives are all such
+    runs in real form (a float64 vector stays float64)."""
+
+    def __init__(self, bonds, weights=None):
+        bonds = [(int(i), int(j)) for (i, j) in bonds]
+        if weights is None:
+            weights = np.ones(len(bonds))
+        self.weights = np.ascontiguousarray(weights, dtype=np.complex128).copy()
+        if self.weights.shape != (len(bonds),):
+            raise ArgumentError("weights must have one entry per bond")
+        self.bonds = bonds
+        self._i = np.ascontiguousarray([b[0] for b in bonds], dtype=np.int32)
+        self._j = np.ascontiguousarray([b[1] for b in bonds], dtype=np.int32)
+        self._re = np.ascontiguousarray(self.weights.real)
+        self._im = np.ascontiguousarray(self.weights.imag) if np.any(self.weights.imag != 0.0) else None
+
+    @property
+    def is_real(self):
+        return self._im is None
+
+    def __repr__(self):
+        return f"HoppingDrive(bonds={len(self.bonds)}, {'real' if self.is_real else 'complex'})"
+
+
+def exchange_drive(model, bonds=None, weights=None):
+    """sum_b w_b (S^+_i S^-_j + S^-_i S^+_j).  By default over the model's own hop bonds with their own amplitudes t_b, so that
+    H0 + f(t) * exchange_drive(model) is the model with its exchange scaled by 1 + f(t): f is the relative modulation dJ/J."""
+    if bonds is None:
+        if weights is not None:
+            raise ArgumentError("weights need their bonds")
+        bonds = [(i, j) for (i, j, _t) in model.hopping_list]
+        weights = [t for (_i, _j, t) in model.hopping_list]
+    return HoppingDrive(bonds, weights)
+
+
+def current_drive(model, weights=None):
+    """J_w = sum_b w_b i t_b (S^+_i S^-_j - S^-_i S^+_j) over the model's hop list (weights None: ones, the total current): the
+    operator of spin_current as a hopping drive, z_b = i w_b t_b."""
+    n = len(model.hopping_list)
+    w = np.ones(n) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (n,):
+        raise ArgumentError(f"weights must have one entry per hop bond ({n})")
+    return HoppingDrive([(i, j) for (i, j, _t) in model.hopping_list], [1j * (w[b] * t) for b, (_i, _j, t) in enumerate(model.hopping_list)])
+
+
+def _displacement(i, j, L, periodic):
+    if not periodic:
+        return j - i
+    r = (j - i) % L
+    if 2 * r == L:
+        raise ArgumentError("a displacement of exactly +-L/2 on the ring has no minimum image")
+    return r if 2 * r < L else r - L
+
+
+def peierls_drives(model, boundary="open"):
+    """The Peierls phase of a uniform vector potential A(t) on the model's hop bonds, convention
+
+        t_b (e^{i A (j - i)} S^+_i S^-_j + h.c.)   for the bond (i, j, t_b),
+
+    as hopping drives.  With delta = j - i the bond term is t_b (S^+ S^- + h.c.) + (cos(delta A) - 1) t_b (S^+ S^- + h.c.)
+    + sin(delta A) i t_b (S^+ S^- - S^- S^+), so per distinct |delta| (bonds with delta < 0 are turned round)
+
+        T_delta = sum_b t_b (S^+_i S^-_j + h.c.),    J_delta = sum_b i t_b (S^+_i S^-_j - S^-_i S^+_j)   (the spin current of the class)
+
+    and H(t) = H0 + sum_delta [(cos(delta A(t)) - 1) T_delta + sin(delta A(t)) J_delta] exactly.  Returns (drives, displacements):
+    drives = [T_d1, J_d1, T_d2, J_d2, ...] for displacements = [d1, d2, ...] ascending; peierls_functions(A, displacements) gives the
+    coefficient functions in the same order.  boundary "periodic": delta is the minimum image on a ring of L sites; a displacement of
+    exactly L/2 has none and is refused, as energy_current_terms refuses it."""
+    if boundary not in ("open", "periodic"):
+        raise ArgumentError("boundary must be \"open\" or \"periodic\"")
+    classes = {}
+    for (i, j, t) in model.hopping_list:
+        d = _displacement(i, j, model.L, boundary == "periodic")
+        if d < 0:
+            i, j, d = j, i, -d
+        if d == 0:
+            continue
+        classes.setdefault(d, []).append((i, j, t))
+    drives, disp = [], sorted(classes)
+    for d in disp:
+        bonds = [(i, j) for (i, j, _t) in classes[d]]
+        ts = np.array([t for (_i, _j, t) in classes[d]], dtype=np.float64)
+        drives += [HoppingDrive(bonds, ts), HoppingDrive(bonds, 1j * ts)]
+    return drives, disp
+
+
+def peierls_functions(A, displacements):
+    """The coefficient functions of peierls_drives' list for the vector potential A(t) (a callable): per displacement delta,
+    t -> cos(delta A(t)) - 1 for T_delta and t -> sin(delta A(t)) for J_delta.
+
+    Sign convention: the bond (i, j) carries e^{+i A (j - i)} on S^+_i S^-_j.  The unitary exp(-i A(t) sum_i i S^z_i) removes the phase
+    and leaves the length-gauge Hamiltonian H0 + E(t) sum_i i S^z_i with E = -dA/dt: the same physics is the existing gradient_drive
+    with f(t) = -dA/dt (for A(t0) = 0 the two states agree at every time at which A returns to 0; S^z observables agree always)."""
+    fs = []
+    for d in displacements:
+        d = float(d)
+        fs.append(lambda t, d=d: math.cos(d * float(A(t))) - 1.0)
+        fs.append(lambda t, d=d: math.sin(d * float(A(t))))
+    return fs
+
+
+def _split(drives):
+    """(drives as a list, positions of the diagonal drives, positions of the hopping drives)"""
+    if isinstance(drives, (DiagonalDrive, HoppingDrive)):
+        drives = [drives]
+    drives = list(drives)
+    di = [k for k, d in enumerate(drives) if isinstance(d, DiagonalDrive)]
+    hi = [k for k, d in enumerate(drives) if isinstance(d, HoppingDrive)]
+    if len(di) + len(hi) != len(drives):
+        raise ArgumentError("drives must be DiagonalDrive or HoppingDrive objects")
+    return drives, di, hi
+
+
+def _pack_hops(hops):
+    """(ctypes array of sd_hop_drive or None, KH): the array points into the drives' own arrays, which the caller keeps alive"""
+    KH = len(hops)
+    if KH == 0:
+        return None, 0
+    arr = (_lib.sd_hop_drive * KH)()
+    for k, d in enumerate(hops):
+        arr[k].n = len(d.bonds)
+        if len(d.bonds):
+            arr[k].i, arr[k].j = d._i.ctypes.data_as(_ip), d._j.ctypes.data_as(_ip)
+            arr[k].re = d._re.ctypes.data_as(_dp)
+            if d._im is not None:
+                arr[k].im = d._im.ctypes.data_as(_dp)
+    return arr, KH
+
+
+def _permute_columns(coef, di, hi):
+    """the caller's coefficient columns in the library's order: the diagonal drives first, then the hopping drives"""
+    coef = np.asarray(coef, dtype=np.float64)
+    return np.ascontiguousarray(coef[..., di + hi])
+
+
 def _as_list(drives):
     if isinstance(drives, DiagonalDrive):
         return [drives]
@@ -100,10 +248,19 @@ def _pack(model, drives):
 
 
 def drive_check(model, drives):
-    """Raises ArgumentError when the library would refuse the drives for this model (sd_drive_check): more than 16 drives, more than
-    128 zz terms in all, a site outside 1..L, a bond with i == j, a weight that is not finite."""
-    arr, K, _keep = _pack(model, drives)
-    check(lib().sd_drive_check(model.h, arr, K), None if model.ctx is None else model.ctx.h)
+    """Raises ArgumentError when the library would refuse the drives for this model (sd_drive_check, sd_hop_drive_check): more than 16
+    drives, more than 128 zz terms or more than 128 hop terms in all, a site outside 1..L, a bond with i == j, a weight that is not
+    finite."""
+    drives, di, hi = _split(drives)
+    ch = None if model.ctx is None else model.ctx.h
+    arr, K, _keep = _pack(model, [drives[k] for k in di])
+    check(lib().sd_drive_check(model.h, arr, K), ch)
+    if hi:
+        if len(drives) > MAX_DRIVES:
+            raise ArgumentError(f"diagonal and hopping drives together must be at most {MAX_DRIVES}")
+        hops = [drives[k] for k in hi]
+        harr, KH = _pack_hops(hops)
+        check(lib().sd_hop_drive_check(model.h, harr, KH), ch)
 
 
 def _coefs(coefs, K):
@@ -149,14 +306,29 @@ def diagonal_apply(psi, model, drives, coefs, y=None, out=None):
 def driven_apply(out, psi, model, drives, coefs):
     """out = (H0 + sum_k coefs[k] D_k) psi: the built-in apply and the drive kernel behind it (sd_driven_apply).  With drives and
     coefs bound -- functools.partial, or a lambda (out, psi, m) -- it is an `applyH=` for every solver that takes one."""
-    arr, K, _keep = _pack(model, drives)
-    c = _coefs(coefs, K)
+    drives, di, hi = _split(drives)
+    arr, K, _keep = _pack(model, [drives[k] for k in di])
     code = _dtype_code(psi)
     if _dtype_code(out) != code:
         raise ArgumentError("out and psi must have the same element type")
     if len(out) != len(psi):
         raise DimensionMismatch("length(out) != length(psi)")
     ctx = model.ctx
+    if hi:
+        hops = [drives[k] for k in hi]
+        harr, KH = _pack_hops(hops)
+        c = _permute_columns(_coefs(coefs, K + KH), di, hi)
+        if _is_torch(psi):
+            _bind_torch_stream(model, psi)
+            _bind_torch_stream(model, out)
+            check(lib().sd_driven_hop_apply_dev(ctx.h, model.h, code, psi.data_ptr(), len(psi), arr, K, harr, KH, c.ctypes.data_as(_dp),
+                                                out.data_ptr()), ctx.h)
+        else:
+            _check_host(out, "out"); _check_host(psi, "psi")
+            check(lib().sd_driven_hop_apply(ctx.h, model.h, code, psi.ctypes.data, len(psi), arr, K, harr, KH, c.ctypes.data_as(_dp),
+                                            out.ctypes.data), ctx.h)
+        return out
+    c = _coefs(coefs, K)
     if _is_torch(psi):
         _bind_torch_stream(model, psi)
         _bind_torch_stream(model, out)
@@ -225,11 +397,14 @@ def stage_evolve(model, psi0, drives, tau, coef, kry_m=30, return_info=False):
     device throughout.  Returns the final state (complex128, normalised by every stage, as krylov_time_evolve): a new torch tensor
     for a torch psi0, a numpy vector otherwise.  return_info: also a dict with the stages run, the operator applications and the
     smallest Lanczos beta seen."""
-    arr, K, _keep = _pack(model, drives)
+    drives, di, hi = _split(drives)
+    arr, K, _keep = _pack(model, [drives[k] for k in di])
     tau = np.ascontiguousarray(np.atleast_1d(tau), dtype=np.float64)
-    coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(len(tau), K) if K else np.zeros((len(tau), 0))
     if len(tau) < 1:
         raise ArgumentError("at least one stage")
+    if hi:
+        return _stage_evolve_hop(model, psi0, drives, di, hi, arr, K, tau, coef, kry_m, return_info)
+    coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(len(tau), K) if K else np.zeros((len(tau), 0))
     info = _lib.sd_driven_info()
     ctx = model.ctx
     cp = coef.ctypes.data_as(_dp) if K else None
@@ -249,6 +424,71 @@ def stage_evolve(model, psi0, drives, tau, coef, kry_m=30, return_info=False):
                                      int(kry_m), out.ctypes.data, C.byref(info)), ctx.h)
     if return_info:
         return out, {"stages": int(info.stages), "applies": int(info.applies), "min_beta": float(info.min_beta)}
+    return out
+
+
+def _stage_evolve_hop(model, psi0, drives, di, hi, arr, K, tau, coef, kry_m, return_info):
+    """stage_evolve with hopping drives in the list (sd_driven_hop_evolve): the coefficient columns go to the library with the diagonal
+    drives first"""
+    hops = [drives[k] for k in hi]
+    harr, KH = _pack_hops(hops)
+    coef = _permute_columns(np.asarray(coef, dtype=np.float64).reshape(len(tau), K + KH), di, hi)
+    info = _lib.sd_driven_info()
+    ctx = model.ctx
+    cp = coef.ctypes.data_as(_dp)
+    if _is_torch(psi0):
+        import torch
+        code = _dtype_code(psi0)
+        _bind_torch_stream(model, psi0)
+        out = torch.empty(len(psi0), dtype=torch.complex128, device=psi0.device)
+        check(lib().sd_driven_hop_evolve_dev(ctx.h, model.h, code, psi0.data_ptr(), len(psi0), arr, K, harr, KH, len(tau),
+                                             tau.ctypes.data_as(_dp), cp, int(kry_m), out.data_ptr(), C.byref(info)), ctx.h)
+    else:
+        x = np.ascontiguousarray(psi0)
+        if x.dtype not in (np.float64, np.complex128):
+            x = x.astype(np.complex128 if np.iscomplexobj(x) else np.float64)
+        out = np.empty(len(x), dtype=np.complex128)
+        check(lib().sd_driven_hop_evolve(ctx.h, model.h, _dtype_code(x), x.ctypes.data, len(x), arr, K, harr, KH, len(tau),
+                                         tau.ctypes.data_as(_dp), cp, int(kry_m), out.ctypes.data, C.byref(info)), ctx.h)
+    if return_info:
+        return out, {"stages": int(info.stages), "applies": int(info.applies), "min_beta": float(info.min_beta)}
+    return out
+
+
+def hopping_apply(psi, model, drives, coefs, y=None, out=None):
+    """(sum_k coefs[k] B_k) psi for hopping drives, plus y when given (y may be `out`).  Returns `out` (a new vector by default).  A
+    list with complex weights needs a complex psi."""
+    drives, di, hi = _split(drives)
+    if di:
+        raise ArgumentError("hopping_apply takes HoppingDrive objects")
+    harr, KH = _pack_hops(drives)
+    c = _coefs(coefs, KH)
+    code = _dtype_code(psi)
+    ctx = model.ctx
+    if _is_torch(psi):
+        import torch
+        _bind_torch_stream(model, psi)
+        if out is None:
+            out = torch.empty_like(psi)
+        if _dtype_code(out) != code or (y is not None and _dtype_code(y) != code):
+            raise ArgumentError("psi, y and out must have the same element type")
+        if len(out) != len(psi) or (y is not None and len(y) != len(psi)):
+            raise DimensionMismatch("psi, y and out must have the same length")
+        check(lib().sd_hop_apply_dev(ctx.h, model.h, code, psi.data_ptr(), len(psi), harr, KH, c.ctypes.data_as(_dp),
+                                     None if y is None else y.data_ptr(), out.data_ptr()), ctx.h)
+        return out
+    _check_host(psi, "psi")
+    if out is None:
+        out = np.empty_like(psi)
+    _check_host(out, "out")
+    if y is not None:
+        _check_host(y, "y")
+    if out.dtype != psi.dtype or (y is not None and y.dtype != psi.dtype):
+        raise ArgumentError("psi, y and out must have the same element type")
+    if len(out) != len(psi) or (y is not None and len(y) != len(psi)):
+        raise DimensionMismatch("psi, y and out must have the same length")
+    check(lib().sd_hop_apply(ctx.h, model.h, code, psi.ctypes.data, len(psi), harr, KH, c.ctypes.data_as(_dp),
+                             None if y is None else y.ctypes.data, out.ctypes.data), ctx.h)
     return out
 
 
@@ -312,3 +552,20 @@ def instantaneous_energy(psi, model, drives, coefs):
     out = np.empty_like(x)
     driven_apply(out, x, model, drives, coefs)
     return float(np.vdot(x, out).real)
+
+
+def drive_expectation(psi, model, drives):
+    """<psi|O_k|psi> for every drive of a mixed list (nothing divided by <psi|psi>): diagonal drives as diagonal_expectation, hopping
+    drives as sum_b 2 Re(z_b <S^+_i S^-_j>) from the "+-" correlation matrix"""
+    from .observables import correlation_matrix
+    drives, di, hi = _split(drives)
+    drive_check(model, drives)
+    vals = np.zeros(len(drives))
+    if di:
+        vals[di] = diagonal_expectation(psi, model, [drives[k] for k in di])
+    if hi:
+        P = correlation_matrix(psi, model, "+-")
+        for k in hi:
+            d = drives[k]
+            vals[k] = sum(2.0 * (complex(z) * complex(P[i - 1, j - 1])).real for (i, j), z in zip(d.bonds, d.weights))
+    return vals
